@@ -5,6 +5,12 @@
   python bench.py [--gpus N --steps K --warmup W]            (N = 1)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
+A plain run sets up, warms up, times the K steps and prints the headline
+line.  --dump-outputs DIR also writes the last timed step's output to
+DIR/<name>.npy (a fixed seeded sample where it is large).  --full adds
+everything reported beside the headline: the CPU baselines, ceiling probes,
+parity checks, variants, sweeps, RCCL comparison and configs 4/5 named below.
+
 N = 1 runs BASELINE config 2 — the single-GPU form of the metric: the device
 MPI.Op kernel reduces 8 rank buffers of 256 MiB f32 with SUM in HBM
 (mpigx_reduce_local_multi, MPICH association).  One step = one kernel launch
@@ -44,6 +50,12 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--mib", type=int, default=256)
     p.add_argument("--nbuf", type=int, default=8)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything reported beside the headline: CPU baselines, ceiling probes, parity "
+                        "checks, variants, sweeps, RCCL, configs 4/5 (the --no-* options trim this)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                        "(float32; an output above 16 MiB as a fixed seeded sample of its elements)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-iters", type=int, default=30)
     p.add_argument("--no-rccl", action="store_true", help="skip the RCCL comparison (N>1)")
@@ -51,6 +63,33 @@ def parse():
     p.add_argument("--no-sweep", action="store_true",
                    help="N=1: skip the size sweep (rocprof runs, so the headline kernel's stats hold 256 MiB launches only)")
     return p.parse_args()
+
+
+DUMP_MAX_BYTES = 16 << 20  # per dumped array (the whole dump stays far below 64 MB)
+
+
+def dump_output(dirname, name, t, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: tensor `t`, an array the caller of the timed path
+    receives, as dirname/name.npy in float32 (float64 data stays float64).  An
+    output above max_bytes is cut to a fixed sample of distinct elements: the
+    output is divided into as many equal spans as elements are kept, and one
+    position per span is drawn from a generator seeded by the output's length
+    alone, so two runs (or two builds) with the same arguments write the same
+    elements."""
+    import numpy as np
+    import torch
+    flat = t.detach().reshape(-1)
+    flat = flat if flat.dtype == torch.float64 else flat.to(torch.float32)
+    keep = max_bytes // flat.element_size()
+    if flat.numel() > keep:
+        n = flat.numel()
+        lo = np.arange(keep + 1, dtype=np.int64) * n // keep  # span bounds, each span >= 1 element
+        idx = lo[:-1] + np.random.default_rng(n).integers(0, lo[1:] - lo[:-1])
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, f"{name}.npy")
+    np.save(path, flat.cpu().numpy())
+    return path
 
 
 def cpu_baseline_local(nbuf, mib, iters):
@@ -208,7 +247,10 @@ def bench_local(args):
     import torch
     import mpigx as MPI
 
-    cpu = None if args.no_cpu_baseline else cpu_baseline_local(args.nbuf, args.mib, args.cpu_iters)
+    # a plain run sets up, warms up, times the K steps and prints the headline;
+    # everything reported beside it (CPU baselines, ceiling probes, parity
+    # check, variants, sweep) runs with --full only
+    cpu = cpu_baseline_local(args.nbuf, args.mib, args.cpu_iters) if args.full and not args.no_cpu_baseline else None
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     count = args.mib << 18
@@ -273,7 +315,7 @@ def bench_local(args):
             torch.cuda.synchronize()
             return default
 
-    probes = len(ins) in (1, 2, 4, 8)
+    probes = args.full and len(ins) in (1, 2, 4, 8)
     read_ms = guarded("read_probe", lambda: [read_probe_ms()], []) if probes else []
     mix_ms = guarded("mix_probe", lambda: [mix_probe_ms()], []) if probes else []
     for _ in range(args.warmup):
@@ -292,6 +334,14 @@ def bench_local(args):
     wall = (time.perf_counter() - t0) / args.steps
     kern_ms = e0.elapsed_time(e1) / args.steps
     algo = (args.nbuf + 1) * S
+    if args.dump_outputs:  # the last timed step's output, before anything else writes `out`
+        dump_output(args.dump_outputs, "out", out)
+    if not args.full:
+        print(json.dumps(build_local_line({
+            "nbuf": args.nbuf, "mib": args.mib, "steps": args.steps, "warmup": args.warmup, "wall_s": wall,
+            "kern_ms": kern_ms, "read_ms": [], "mix_ms": [], "parity": None, "variants": None, "sweep": None,
+            "cpu": None, "cpu_ar": None, "traffic": None, "traffic_src": None})), flush=True)
+        return
     if read_ms:
         read_ms += guarded("read_probe", lambda: [read_probe_ms()], [])
     if mix_ms:
@@ -582,6 +632,23 @@ def bench_allreduce(args):
                "pullpush_ns_per_MiB": round(costs[2], 1),
                "basis": "device time of one 256 MiB call each, max over ranks decides (rank 0's shown)"}
     t, kern, send, recv = time_ar(S, args.steps, args.warmup, keep=True)
+    if args.dump_outputs and rank == 0:  # every rank's recvbuf holds the same sum
+        dump_output(args.dump_outputs, "recv", recv)
+    if not args.full:
+        # a plain run ends here: the headline alone, no checks, sweeps or baselines
+        del send, recv
+        if rank == 0:
+            print(json.dumps(build_coll_line({
+                "n": n, "mib": args.mib, "steps": args.steps, "warmup": args.warmup, "t": t, "kern": kern,
+                "same_device": same_device, "ar_tune": ar_tune, "traffic": None, "traffic_src": None, "xg": None,
+                "cpu_ar": None, "correct": None, "tune_classes": None, "probe": None, "phases": None,
+                "section_s": {"headline": round(time.perf_counter() - t_start, 2)}, "sweep": None, "rccl": None,
+                "cfg4": None, "tune_classes4": None, "cfg5": None, "cfg5_ok": None, "errors": None})), flush=True)
+        try:
+            MPI.Finalize()
+        finally:
+            dist.destroy_process_group()
+        return
     correct = check_sample(recv, S // 4, "timed buffers, default algorithm")
     del send, recv
 

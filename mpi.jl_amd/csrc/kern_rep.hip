@@ -23,11 +23,36 @@
 #define MPIGX_CAT(a, b) MPIGX_CAT2(a, b)
 #define MPIGX_CAT4(a, b, c, d) MPIGX_CAT(MPIGX_CAT(a, b), MPIGX_CAT(c, d))
 
-// per-op entry points of this rep: launch_<kind>_<name>_o<op code>
-#define MPIGX_FOLD_FN(K) MPIGX_CAT4(launch_fold_, MPIGX_REP_NAME, _o, K)
-#define MPIGX_RING_FN(K) MPIGX_CAT4(launch_ring_, MPIGX_REP_NAME, _o, K)
-#define MPIGX_SCAN_FN(K) MPIGX_CAT4(launch_scan_, MPIGX_REP_NAME, _o, K)
-#define MPIGX_ACC_FN(K) MPIGX_CAT4(launch_acc_, MPIGX_REP_NAME, _o, K)
+// MPIGX_OP_NAME(K): the rep whose part defines op K's entry points.  That is
+// this rep, except in the dispatchers of a signed integer rep (part 6 built
+// with -DMPIGX_SHARE_NAME=<unsigned twin>, see Makefile): SUM, PROD and the
+// logical and bitwise ops give the same bits on either signedness (add_ / mul_
+// in device.hpp compute through the unsigned type), so those go to the twin's
+// kernels and only MIN / MAX (parts 2, 3) are built for the signed rep.
+#ifndef MPIGX_SHARE_NAME
+#define MPIGX_SHARE_NAME MPIGX_REP_NAME
+#elif MPIGX_PART == 0 || MPIGX_PART == 1 || MPIGX_PART == 4 || MPIGX_PART == 5
+#error "a rep that shares its twin's sign-agnostic ops builds parts 2, 3 and 6 only"
+#endif
+#define MPIGX_OP_NAME_0 MPIGX_SHARE_NAME
+#define MPIGX_OP_NAME_1 MPIGX_SHARE_NAME
+#define MPIGX_OP_NAME_2 MPIGX_REP_NAME
+#define MPIGX_OP_NAME_3 MPIGX_REP_NAME
+#define MPIGX_OP_NAME_4 MPIGX_SHARE_NAME
+#define MPIGX_OP_NAME_5 MPIGX_SHARE_NAME
+#define MPIGX_OP_NAME_6 MPIGX_SHARE_NAME
+#define MPIGX_OP_NAME_7 MPIGX_SHARE_NAME
+#define MPIGX_OP_NAME_8 MPIGX_SHARE_NAME
+#define MPIGX_OP_NAME_9 MPIGX_SHARE_NAME
+#define MPIGX_OP_NAME_16 MPIGX_REP_NAME
+#define MPIGX_OP_NAME_17 MPIGX_REP_NAME
+#define MPIGX_OP_NAME(K) MPIGX_CAT(MPIGX_OP_NAME_, K)
+
+// per-op entry points: launch_<kind>_<name>_o<op code>
+#define MPIGX_FOLD_FN(K) MPIGX_CAT4(launch_fold_, MPIGX_OP_NAME(K), _o, K)
+#define MPIGX_RING_FN(K) MPIGX_CAT4(launch_ring_, MPIGX_OP_NAME(K), _o, K)
+#define MPIGX_SCAN_FN(K) MPIGX_CAT4(launch_scan_, MPIGX_OP_NAME(K), _o, K)
+#define MPIGX_ACC_FN(K) MPIGX_CAT4(launch_acc_, MPIGX_OP_NAME(K), _o, K)
 
 namespace mpigx {
 namespace {
@@ -174,8 +199,8 @@ int occ_op(int kind, int a, int b) {
 
 // Per-op entry points: declared for every op code here (the dispatchers of
 // part 6 reference only the valid ones), defined by the part that owns the op.
-#define MPIGX_ARZC_FN(K) MPIGX_CAT4(launch_arzc_, MPIGX_REP_NAME, _o, K)
-#define MPIGX_OCC_FN(K) MPIGX_CAT4(occupancy_, MPIGX_REP_NAME, _o, K)
+#define MPIGX_ARZC_FN(K) MPIGX_CAT4(launch_arzc_, MPIGX_OP_NAME(K), _o, K)
+#define MPIGX_OCC_FN(K) MPIGX_CAT4(occupancy_, MPIGX_OP_NAME(K), _o, K)
 #define MPIGX_DECL_OP(K)                                                                               \
   hipError_t MPIGX_ARZC_FN(K)(int nmax, int shape, int ag, dim3 grid, hipStream_t s, const FoldArgs& a);      \
   int MPIGX_OCC_FN(K)(int kind, int a, int b);                                                         \

@@ -111,3 +111,71 @@ def test_cpu_reference_sweep_runs_here():
     for d in ("int32", "int64"):
         for o in ("BAND", "BOR", "MAX"):
             assert j[f"{d}_{o}_1024"]["scan_algbw_GBps"] > 0
+
+
+def test_plain_local_line_holds_the_headline():
+    """A run without --full measures the timed steps only: the headline keys
+    mean what they mean in the full line, the sections beside them are null."""
+    m = {"nbuf": 8, "mib": 256, "steps": 7, "warmup": 2, "wall_s": 0.3833e-3, "kern_ms": 0.3823, "read_ms": [],
+         "mix_ms": [], "parity": None, "variants": None, "sweep": None, "cpu": None, "cpu_ar": None, "traffic": None,
+         "traffic_src": None}
+    line = bench.build_local_line(m)
+    json.dumps(line)
+    assert line["metric"] == "Allreduce! busbw GB/s (256MiB f32 SUM) at 1/2/4/8 GPUs; % of xGMI/HBM peak"
+    assert abs(line["value"] - 2415919104 / 0.3833e-3 / 1e9) < 0.01
+    assert (line["unit"], line["higher_is_better"], line["dtype"]) == ("GB/s", True, "f32")
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] == 0.3833
+    assert line["cpu_baseline"] is None and line["sweep_local_f32_sum"] is None and line["errors"] is None
+    assert line["roofline"]["frac"] is not None and line["roofline"]["peak_measured"] is None
+
+
+def test_options_full_and_dump_outputs(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_output_is_fixed_and_bounded(tmp_path):
+    import numpy as np
+    import torch
+    d = str(tmp_path / "dump")
+    small = torch.arange(1000, dtype=torch.float32) * 0.5
+    a = np.load(bench.dump_output(d, "small", small))
+    assert a.dtype == np.float32 and np.array_equal(a, small.numpy())  # below the bound: the whole output
+    big = torch.arange(100000, dtype=torch.float32)
+    b = np.load(bench.dump_output(d, "big", big, max_bytes=4096))
+    assert b.dtype == np.float32 and b.nbytes == 4096
+    # distinct positions in increasing order, one from each of 1024 equal spans
+    lo = np.arange(1025, dtype=np.int64) * 100000 // 1024
+    assert np.all(np.diff(b) > 0) and np.all(lo[:-1] <= b) and np.all(b < lo[1:])
+    b2 = np.load(bench.dump_output(d, "big2", big, max_bytes=4096))
+    assert np.array_equal(b, b2)  # the same elements on every run
+    assert np.load(bench.dump_output(d, "f64", small.double())).dtype == np.float64
+    assert np.load(bench.dump_output(d, "bf16", small.bfloat16())).dtype == np.float32
+    assert sorted(os.listdir(d)) == ["bf16.npy", "big.npy", "big2.npy", "f64.npy", "small.npy"]
+
+
+def test_plain_coll_line_holds_the_headline():
+    """The N > 1 line of a run without --full: the headline from the timed
+    steps, every section beside it null or empty, still one JSON line."""
+    m = {"n": 2, "mib": 256, "steps": 10, "warmup": 3, "t": 0.3232e-3, "kern": 0.3e-3, "same_device": True,
+         "ar_tune": {"choice": "pull-push two-shot"}, "traffic": None, "traffic_src": None, "xg": None,
+         "cpu_ar": None, "correct": None, "tune_classes": None, "probe": None, "phases": None,
+         "section_s": {"headline": 0.7}, "sweep": None, "rccl": None, "cfg4": None, "tune_classes4": None,
+         "cfg5": None, "cfg5_ok": None, "errors": None}
+    line = bench.build_coll_line(m)
+    json.dumps(line)
+    assert line["metric"] == "Allreduce! busbw GB/s (256MiB f32 SUM) at 1/2/4/8 GPUs; % of xGMI/HBM peak"
+    assert abs(line["value"] - (256 << 20) / 0.3232e-3 / 1e9) < 0.01  # busbw factor 2(n-1)/n = 1 at n = 2
+    assert (line["unit"], line["higher_is_better"], line["dtype"], line["n_gpus"]) == ("GB/s", True, "f32", 2)
+    assert line["steps"] == 10 and line["warmup"] == 3 and line["ms_per_step"] == 0.3232
+    assert line["roofline"]["bound"] == "hbm (same-device IPC)" and line["roofline"]["frac"] is not None
+    for k in ("cpu_baseline", "correct", "sweep_mpigx_busbw", "rccl_busbw", "config4_bcast_allgather_alltoall",
+              "errors"):
+        assert line[k] is None, k
+    m.update(n=8, same_device=False)
+    line = bench.build_coll_line(m)
+    assert line["roofline"]["bound"] == "xgmi" and line["roofline"]["traffic"] is None and line["n_gpus"] == 8

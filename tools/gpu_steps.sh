@@ -14,8 +14,8 @@ T=${TAG:-gpu}
 STOP_ON_FAIL=${STOP_ON_FAIL:-0}
 declare -A PRE=(
   [pytest]="pytest|900|python -u -m pytest tests -m gpu -x -v --timeout 500 --timeout-method thread"
-  [bench1]="bench1|240|python bench.py"
-  [bench2]="bench2|300|python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline"
+  [bench1]="bench1|240|python bench.py --full"
+  [bench2]="bench2|300|python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 10 --warmup 3 --full --no-cpu-baseline"
   [repro8]="repro8|300|python3 tools/scan_repro_launch.py 8"
 )
 for spec in "$@"; do

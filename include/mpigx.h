@@ -287,6 +287,25 @@ int mpigx_scan(const void *sendbuf, void *recvbuf, int count, int datatype, int 
 /* MPI_Exscan   — collective.jl:834-842 (rank 0's recvbuf is left untouched) */
 int mpigx_exscan(const void *sendbuf, void *recvbuf, int count, int datatype, int op,
                  mpigx_comm_t comm);
+/* Reduce-scatter (MPI.jl v0.14.2 wraps neither call; MPICH 3.3.2 semantics).
+ * Rank r receives the reduction of elements [displ[r], displ[r] + recvcounts[r])
+ * of every rank's sendbuf, displ = prefix sums of recvcounts (the block form:
+ * recvcount on every rank).  With MPIGX_IN_PLACE the input, sum(recvcounts)
+ * elements, is taken from recvbuf and the result is left at its start.  Ranks
+ * with an empty block take part like the others; a total of 0 returns at once.
+ * MPIGX_ORDER_MPICH is MPICH's association: recursive halving below 512 KiB
+ * of all blocks together, pairwise exchange from there up (both restated in
+ * tests/redscat_model.py); MPIGX_ORDER_LINEAR the rank-ordered left fold of
+ * each block.  User-defined ops fold each block in Reduce's order (rank order,
+ * from the highest contributing rank down); MPICH's association for
+ * non-commutative user ops in reduce-scatter is NOT pinned.  Communicators of
+ * up to 8 ranks. */
+/* MPI_Reduce_scatter_block (sendbuf may be MPIGX_IN_PLACE) */
+int mpigx_reduce_scatter_block(const void *sendbuf, void *recvbuf, int recvcount,
+                               int datatype, int op, mpigx_comm_t comm);
+/* MPI_Reduce_scatter (recvcounts: host int[n], elements; sendbuf may be MPIGX_IN_PLACE) */
+int mpigx_reduce_scatter(const void *sendbuf, void *recvbuf, const int *recvcounts,
+                         int datatype, int op, mpigx_comm_t comm);
 
 /* ---- local ops (config 2; operators.jl built-in Op set on device) ------- */
 /* MPI_Reduce_local (mpi.h:1357): inoutbuf[i] = op(inoutbuf[i], inbuf[i]).

@@ -38,6 +38,7 @@
 #include "common.hpp"
 #include "handles.hpp"
 #include "launch.hpp"
+#include "rs_launch.hpp"
 #include "runtime.hpp"
 
 using namespace mpigx;
@@ -3887,6 +3888,329 @@ static int lower_reduce_type(int* datatype, int* count) {
   *datatype = d.basic;
   *count = (int)n;
   return MPIGX_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------
+// Reduce_scatter_block / Reduce_scatter (kernels: redscat.hpp rs_kernel).
+// Rank r receives the reduction of block r = elements [displ[r], displ[r] +
+// cnt[r]) of every rank's sendbuf.  Everything the kernel needs is resolved
+// here per rank: the leaves' pointers already offset to my block, the
+// schedule, the partition.
+// ---------------------------------------------------------------------------
+static RsLauncher rs_launcher(int rep) {
+  static const RsLauncher ls[R_COUNT] = {launch_rs_i8,  launch_rs_u8,  launch_rs_i16, launch_rs_u16, launch_rs_i32,
+                                         launch_rs_u32, launch_rs_i64, launch_rs_u64, launch_rs_f32, launch_rs_f64,
+                                         launch_rs_c64, launch_rs_c128, launch_rs_bf16};
+  return rep >= 0 && rep < R_COUNT ? ls[rep] : nullptr;
+}
+// the rep whose rs_rep.hip object holds the kernels of (rep, op): a signed
+// integer's own for MIN / MAX, its unsigned twin's for every other op
+static int rs_rep_for(int rep, int oc) {
+  const bool is_signed = rep == R_I8 || rep == R_I16 || rep == R_I32 || rep == R_I64;
+  return (is_signed && oc != O_MIN && oc != O_MAX) ? rep + 1 : rep;
+}
+static int rs_occ(int rep, int oc, int nmax, int sched, int shape) {
+  static const RsOccQuery qs[R_COUNT] = {occupancy_rs_i8,  occupancy_rs_u8,  occupancy_rs_i16, occupancy_rs_u16,
+                                         occupancy_rs_i32, occupancy_rs_u32, occupancy_rs_i64, occupancy_rs_u64,
+                                         occupancy_rs_f32, occupancy_rs_f64, occupancy_rs_c64, occupancy_rs_c128,
+                                         occupancy_rs_bf16};
+  static std::mutex mu;
+  static std::vector<std::pair<unsigned, int>> cache;
+  const unsigned key = ((unsigned)rep << 16) | ((unsigned)oc << 8) | ((unsigned)nmax << 4) | ((unsigned)sched << 2) |
+                       (unsigned)shape;
+  std::lock_guard<std::mutex> g(mu);
+  for (auto& e : cache)
+    if (e.first == key) return e.second;
+  const int v = qs[rep](oc, nmax, sched, shape);
+  cache.push_back({key, v});
+  return v;
+}
+
+// The fold of MY block over ptrs[q] (rank q's copy of it).  MPIGX_ORDER_LINEAR:
+// the rank-ordered left fold.  MPIGX_ORDER_MPICH (MPICH 3.3.2, commutative
+// ops; `total_bytes` = all blocks together, the same on every rank):
+//   below kRsPairwiseMin recursive halving — even rank 2q folds as `in` into
+//   odd rank 2q+1 for q < rem (pre-step), the survivors take new ranks, and
+//   the block of new rank d is the balanced tree T(d, j) = op(inout = T(d,
+//   j-1), in = T(d ^ (pof2 >> j), j-1)): leaf i of the distance-1-first tree
+//   with the lower leaf inout is new rank d ^ bitrev(i);
+//   from kRsPairwiseMin up pairwise exchange — acc = x[r], then op(inout =
+//   acc, in = x[(r - i) mod n]) for i = 1 .. n-1.
+static void rs_plan(FoldArgs& a, int n, int r, long long total_bytes, const void* const* ptrs, int order, int* sched) {
+  a.rem = 0;
+  a.owner_mode = 0;
+  a.pof2_log = 0;
+  a.blk_len = 1;
+  a.blk_inv = 1.0;
+  if (order == MPIGX_ORDER_LINEAR) {
+    *sched = S_LINEAR;
+    a.ntree = n;
+    for (int k = 0; k < n; ++k) a.src[k] = ptrs[k];
+    return;
+  }
+  if (total_bytes >= kRsPairwiseMin) {
+    *sched = S_LINEAR;
+    a.ntree = n;
+    for (int i = 0; i < n; ++i) a.src[i] = ptrs[(r - i + n) % n];
+    return;
+  }
+  *sched = S_TREE;
+  const int pof2 = pof2_of(n), rem = n - pof2, L = log2i(pof2);
+  const int d = r < 2 * rem ? r / 2 : r - rem;
+  a.ntree = pof2;
+  int j = 0;
+  for (int i = 0; i < pof2; ++i) {
+    int rev = 0;
+    for (int k = 0; k < L; ++k)
+      if (i & (1 << k)) rev |= 1 << (L - 1 - k);
+    const int q = d ^ rev;
+    if (q < rem) {
+      a.src[i] = ptrs[2 * q + 1];  // inout
+      a.src2[j] = ptrs[2 * q];     // in
+      a.leaf2_rank[j] = (signed char)i;
+      ++j;
+    } else {
+      a.src[i] = ptrs[q + rem];
+    }
+  }
+  a.rem = j;
+}
+
+// `s` = my contribution (sum(cnt) elements; == recv when in place), `recv` my
+// result (cnt[rank] elements).
+static int reduce_scatter_common(mpigx_comm* c, const void* s, void* recv, const long long* cnt, const TypeInfo* t,
+                                 int oc, bool inplace) {
+  const int n = c->n, r = c->rank, es = t->size;
+  const int vec = es >= 16 ? 1 : 16 / es;
+  long long displ[kMaxRanks], total = 0, maxc = 0;
+  for (int q = 0; q < n; ++q) {
+    displ[q] = total;
+    total += cnt[q];
+    maxc = std::max(maxc, cnt[q]);
+  }
+  const long long mine = cnt[r];
+  if (n == 1) return copy_n1(c, recv, s, (size_t)mine * es);
+  if (n > 8) {
+    fprintf(stderr, "[mpigx] rank %d: Reduce_scatter is built for communicators of up to 8 ranks (this one has %d)\n",
+            r, n);
+    return MPIGX_ERR_OTHER;
+  }
+  const int krep = rs_rep_for(t->rep, oc);
+  RsLauncher L = rs_launcher(krep);
+  int nmax = 0, shape = 0, sched = 0;
+  // zero-copy: count, thresholds and knobs are identical on every rank, so is this test
+  if (c->zc_min > 0 && total * es >= c->zc_min) {
+    bool staged;
+    // the view holds my sendbuf twice: no peer touches my recvbuf (a rank
+    // with an empty block may not even have one)
+    const int rc = zc_run(c, s, (void*)s, &staged, [&](const ZcLaunch& z) {
+      FoldArgs a;
+      memset(&a, 0, sizeof a);
+      a.pv = make_view(c);
+      zc_apply(a.pv, z);
+      zc_extents(a.pv, z, n, total * es, 0);
+      a.mode = M_RS_ZC;
+      a.esize = es;
+      a.count = mine;
+      const void* ptrs[kMaxRanks];
+      for (int p = 0; p < n; ++p) ptrs[p] = z.ps[p] ? z.ps[p] + displ[r] * es : nullptr;
+      rs_plan(a, n, r, total * es, ptrs, c->order, &sched);
+      rs_shape(n, sched, a.ntree, a.rem, &nmax, &shape);
+      const int grid = grid_for(c, maxc * es, kernel_cap(c, rs_occ(krep, oc, nmax, sched, shape)));
+      a.slice = rs_slice(mine, grid, vec);
+      char* tmp = nullptr;
+      if (inplace) {
+        // fold into a private temporary; the kernel copies it out after a
+        // whole-launch barrier: every block of every rank has finished reading
+        // my buffer (redscat.hpp)
+        tmp = tmp_get(c, std::max(16ll, mine * es));
+        if (!tmp) return (int)MPIGX_ERR_NO_MEM;
+        a.own = 1;
+        a.recv = tmp;
+        a.send = recv;
+      } else {
+        a.recv = recv;
+      }
+      seal_args(a);
+      const hipError_t he = L(oc, nmax, sched, shape, dim3(grid), c->stream, a);
+      if (tmp) tmp_put(c, tmp, 0);  // (stream order makes the reuse safe)
+      HIPCK(he);
+      note_launch(c, a.pv, grid);
+      if (inplace) c->wfinished += grid;  // rank_barrier_grid's block counter
+      c->epoch += 2;
+      return (int)MPIGX_SUCCESS;
+    });
+    if (rc || !staged) return rc;
+    if (c->zc_require) return MPIGX_ERR_INTERN;  // tests: the path must not fall back
+  }
+  // staged: n slots of my arena, one per sender; rounds when a block exceeds a slot
+  if (c->ll_unfenced) {
+    // phase 1 writes into the peers' arenas before any barrier (see allreduce_push)
+    const int rc = barrier_launch(c);
+    if (rc) return rc;
+    c->ll_unfenced = false;
+  }
+  const long long slot_bytes = (long long)(c->stage_bytes / n) / 16 * 16;
+  const long long round = slot_bytes / es / vec * vec;
+  if (round <= 0) return MPIGX_ERR_NO_MEM;
+  // in place: other blocks of my launch still push the region a block would
+  // store its result into (phase 1 cuts my sendbuf by the OWNERS' partitions),
+  // so every round folds into a temporary and copies out after a whole-launch
+  // barrier, as on the zero-copy path.  Round k stores recvbuf[k round, ...),
+  // which later rounds no longer read: they start at (k + 1) round of every block.
+  char* tmp = nullptr;
+  if (inplace) {
+    tmp = tmp_get(c, std::max(16ll, std::min(mine, round) * es));
+    if (!tmp) return MPIGX_ERR_NO_MEM;
+  }
+  for (long long off = 0; off < maxc; off += round) {
+    FoldArgs a;
+    memset(&a, 0, sizeof a);
+    a.pv = make_view(c);
+    a.mode = M_RS_PUSH;
+    a.esize = es;
+    a.count = std::min(std::max(mine - off, 0ll), round);
+    if (inplace) {
+      a.own = 1;
+      a.recv = tmp;
+      a.send = (char*)recv + off * es;
+    } else {
+      a.recv = (char*)recv + off * es;
+    }
+    a.slot_bytes = slot_bytes;
+    for (int p = 0; p < n; ++p) {
+      a.zc_recv[p] = (char*)s + (displ[p] + off) * es;
+      a.zc_avail[p] = std::min(std::max(cnt[p] - off, 0ll), round) * es;
+    }
+    const void* ptrs[kMaxRanks];
+    for (int q = 0; q < n; ++q) ptrs[q] = c->stage + (long long)q * slot_bytes;
+    rs_plan(a, n, r, total * es, ptrs, c->order, &sched);
+    rs_shape(n, sched, a.ntree, a.rem, &nmax, &shape);
+    const int grid = grid_for(c, std::min(maxc - off, round) * es, kernel_cap(c, rs_occ(krep, oc, nmax, sched, shape)));
+    a.slice = rs_slice(a.count, grid, vec);
+    seal_args(a);
+    const hipError_t he = L(oc, nmax, sched, shape, dim3(grid), c->stream, a);
+    if (he != hipSuccess && tmp) tmp_put(c, tmp, 0);
+    HIPCK(he);
+    note_launch(c, a.pv, grid);
+    if (inplace) c->wfinished += grid;
+    c->epoch += 2;
+  }
+  if (tmp) tmp_put(c, tmp, 0);  // (stream order makes the reuse safe)
+  return finish(c);
+}
+
+// user-defined op: block r of every contribution gathered into n slots
+// (Alltoallv), folded in Reduce's order (rank order, from the highest rank
+// down), the result copied into recvbuf
+static int user_reduce_scatter(mpigx_comm* c, UserOp* u, const void* send, void* recv, const long long* cnt,
+                               int datatype) {
+  rt::TypeDesc d;
+  if (rt::type_info(datatype, &d) || !d.contig) return MPIGX_ERR_TYPE;
+  const int n = c->n, r = c->rank;
+  long long total = 0;
+  for (int q = 0; q < n; ++q) total += cnt[q];
+  if (total * d.size > 0x7fffffff) return MPIGX_ERR_COUNT;
+  const void* mine = send == MPIGX_IN_PLACE ? recv : send;
+  const long long slot = cnt[r] * d.size;
+  if (send != MPIGX_IN_PLACE && slot > 0) {  // out of place: the buffers may not overlap
+    const char *s0 = (const char*)send, *s1 = s0 + total * d.size, *o0 = (const char*)recv, *o1 = o0 + slot;
+    if (s0 < o1 && o0 < s1) return MPIGX_ERR_BUFFER;
+  }
+  if (n == 1) return copy_n1(c, recv, mine, (size_t)slot);
+  int scnt[kMaxRanks], sdsp[kMaxRanks], rcnt[kMaxRanks], rdsp[kMaxRanks];
+  long long at = 0;
+  for (int q = 0; q < n; ++q) {
+    scnt[q] = (int)(cnt[q] * d.size);
+    sdsp[q] = (int)at;
+    at += cnt[q] * d.size;
+    rcnt[q] = (int)slot;
+    rdsp[q] = (int)(q * slot);
+  }
+  char* all = tmp_get(c, std::max(16ll, (long long)n * slot));
+  if (!all) return MPIGX_ERR_NO_MEM;
+  int rc = mpigx_alltoallv(mine, scnt, sdsp, MPIGX_BYTE, all, rcnt, rdsp, MPIGX_BYTE, c);
+  if (!rc) rc = user_fold_slots(c, u, all, slot, n, (int)cnt[r], datatype);
+  if (!rc && slot &&
+      hipMemcpyAsync(recv, all + (long long)(n - 1) * slot, (size_t)slot, hipMemcpyDeviceToDevice, c->stream) !=
+          hipSuccess) {
+    (void)hipGetLastError();
+    rc = MPIGX_ERR_INTERN;
+  }
+  c->unflagged = true;  // the copy follows the last flagged launch: finish() drains the stream
+  if (!rc) rc = finish(c);
+  tmp_put(c, all, 0);
+  return rc;
+}
+
+static int reduce_scatter_any(const void* sendbuf, void* recvbuf, const long long* cnt_in, int datatype, int op,
+                              mpigx_comm_t c) {
+  const int n = c->n, r = c->rank;
+  long long cnt[kMaxRanks], total = 0;
+  for (int q = 0; q < n; ++q) {
+    if (cnt_in[q] < 0) return MPIGX_ERR_COUNT;
+    cnt[q] = cnt_in[q];
+    total += cnt[q];
+  }
+  UserOp* u = user_op(op);
+  const TypeInfo* t = nullptr;
+  int oc = 0;
+  if (!u) {
+    // a contiguous derived type of one predefined type: k elements per instance
+    int one = 1, rc;
+    if ((rc = lower_reduce_type(&datatype, &one))) return rc;
+    if ((rc = validate(datatype, op, &t, &oc))) return rc;
+    total = 0;
+    for (int q = 0; q < n; ++q) {
+      cnt[q] *= one;
+      total += cnt[q];
+    }
+  }
+  if (total > 0x7fffffff) return MPIGX_ERR_COUNT;
+  if (total == 0) return MPIGX_SUCCESS;
+  const bool inplace = sendbuf == MPIGX_IN_PLACE;
+  if (!sendbuf || (!recvbuf && (inplace || cnt[r] > 0))) return MPIGX_ERR_BUFFER;
+  if (u) return user_reduce_scatter(c, u, sendbuf, recvbuf, cnt, datatype);
+  const char* s = inplace ? (const char*)recvbuf : (const char*)sendbuf;
+  if (!inplace && cnt[r] > 0) {  // out of place: the buffers may not overlap
+    const char *s1 = s + total * t->size, *o0 = (const char*)recvbuf, *o1 = o0 + cnt[r] * t->size;
+    if (s < o1 && o0 < s1) return MPIGX_ERR_BUFFER;
+  }
+  return reduce_scatter_common(c, s, recvbuf, cnt, t, oc, inplace);
+}
+
+int mpigx_reduce_scatter_block(const void* sendbuf, void* recvbuf, int recvcount, int datatype, int op,
+                               mpigx_comm_t c) {
+  int rc = check_comm(c);
+  if (rc) return rc;
+  long long cnt[kMaxRanks];
+  for (int q = 0; q < c->n; ++q) cnt[q] = recvcount;
+  return reduce_scatter_any(sendbuf, recvbuf, cnt, datatype, op, c);
+}
+
+int mpigx_reduce_scatter(const void* sendbuf, void* recvbuf, const int* recvcounts, int datatype, int op,
+                         mpigx_comm_t c) {
+  int rc = check_comm(c);
+  if (rc) return rc;
+  if (!recvcounts) return MPIGX_ERR_ARG;
+  const int n = c->n;
+  long long cnt[kMaxRanks];
+  for (int q = 0; q < n; ++q) cnt[q] = recvcounts[q];
+  // What selects a path (total bytes: zero-copy or staged, the schedule, the
+  // rounds and the grid) and the partition follow from the counts, which
+  // every rank passes for itself: agreed over the control plane, so a
+  // mismatch fails the call on every rank instead of launching kernels that
+  // wait for each other
+  if (n > 1) {
+    int all[kMaxRanks][kMaxRanks];
+    int mine[kMaxRanks] = {0};
+    for (int q = 0; q < n; ++q) mine[q] = recvcounts[q];
+    if ((rc = host_allgather(c, mine, (int)(sizeof(int) * kMaxRanks), all))) return rc;
+    for (int p = 0; p < n; ++p)
+      for (int q = 0; q < n; ++q)
+        if (all[p][q] != recvcounts[q]) return MPIGX_ERR_COUNT;
+  }
+  return reduce_scatter_any(sendbuf, recvbuf, cnt, datatype, op, c);
 }
 
 int mpigx_allreduce(const void* sendbuf, void* recvbuf, int count, int datatype, int op, mpigx_comm_t c) {

@@ -333,6 +333,60 @@ Scan!(sendbuf::DeviceOrSentinel, recvbuf::ROCBuffer, count::Integer, opfunc, com
     _with_device_op(op -> Scan!(sendbuf, recvbuf, count, op, comm), opfunc, eltype(recvbuf))
 Exscan!(sendbuf::DeviceOrSentinel, recvbuf::ROCBuffer, count::Integer, opfunc, comm::Comm) =
     _with_device_op(op -> Exscan!(sendbuf, recvbuf, count, op, comm), opfunc, eltype(recvbuf))
+# ---------------------------------------------------------------------------
+# Reduce_scatter_block! / Reduce_scatter! (MPI_Reduce_scatter_block,
+# MPI_Reduce_scatter).  MPI.jl v0.14.2 has no method of these names, host-side
+# or otherwise: they are new functions of this module, not extensions of the
+# reference's.  Rank r receives the reduction of block r of every rank's
+# sendbuf; with MPI.IN_PLACE the input is taken from recvbuf and the result
+# is left at its start.
+# ---------------------------------------------------------------------------
+function Reduce_scatter_block!(sendbuf::DeviceOrSentinel, recvbuf::ROCBuffer, count::Integer,
+                               op::Union{Op,MPI_Op}, comm::Comm)
+    total = count * MPI.Comm_size(comm)
+    if sendbuf isa SentinelPtr
+        MPI.@assert_minlength recvbuf total
+    else
+        MPI.@assert_minlength sendbuf total
+        MPI.@assert_minlength recvbuf count
+        @assert eltype(sendbuf) == eltype(recvbuf)
+    end
+    T = eltype(recvbuf)
+    @mpichk ccall((:mpigx_reduce_scatter_block, libmpigx), Cint,
+                  (MPIPtr, MPIPtr, Cint, MPI_Datatype, MPI_Op, Ptr{Cvoid}),
+                  sendbuf, recvbuf, count, Datatype(T), engine_op(op), engine(comm))
+    recvbuf
+end
+function Reduce_scatter!(sendbuf::DeviceOrSentinel, recvbuf::ROCBuffer, counts::AbstractVector{<:Integer},
+                         op::Union{Op,MPI_Op}, comm::Comm)
+    @assert length(counts) == MPI.Comm_size(comm)
+    cc = Vector{Cint}(counts)
+    if sendbuf isa SentinelPtr
+        MPI.@assert_minlength recvbuf sum(counts)
+    else
+        MPI.@assert_minlength sendbuf sum(counts)
+        MPI.@assert_minlength recvbuf counts[MPI.Comm_rank(comm) + 1]
+        @assert eltype(sendbuf) == eltype(recvbuf)
+    end
+    T = eltype(recvbuf)
+    @mpichk ccall((:mpigx_reduce_scatter, libmpigx), Cint,
+                  (MPIPtr, MPIPtr, Ptr{Cint}, MPI_Datatype, MPI_Op, Ptr{Cvoid}),
+                  sendbuf, recvbuf, cc, Datatype(T), engine_op(op), engine(comm))
+    recvbuf
+end
+Reduce_scatter_block!(sendbuf::DeviceOrSentinel, recvbuf::ROCBuffer, count::Integer, opfunc, comm::Comm) =
+    _with_device_op(op -> Reduce_scatter_block!(sendbuf, recvbuf, count, op, comm), opfunc, eltype(recvbuf))
+Reduce_scatter!(sendbuf::DeviceOrSentinel, recvbuf::ROCBuffer, counts::AbstractVector{<:Integer}, opfunc,
+                comm::Comm) =
+    _with_device_op(op -> Reduce_scatter!(sendbuf, recvbuf, counts, op, comm), opfunc, eltype(recvbuf))
+# length-taking and in-place forms
+Reduce_scatter_block!(sendbuf::ROCBuffer, recvbuf::ROCBuffer, opfunc, comm::Comm) =
+    Reduce_scatter_block!(sendbuf, recvbuf, length(recvbuf), opfunc, comm)
+Reduce_scatter_block!(buf::ROCBuffer, count::Integer, opfunc, comm::Comm) =
+    Reduce_scatter_block!(MPI.IN_PLACE, buf, count, opfunc, comm)
+Reduce_scatter!(buf::ROCBuffer, counts::AbstractVector{<:Integer}, opfunc, comm::Comm) =
+    Reduce_scatter!(MPI.IN_PLACE, buf, counts, opfunc, comm)
+
 # the reference's length-taking and in-place forms (collective.jl:707-714,
 # :626-638, :773-783, :847-857) reach the methods above through dispatch on
 # ROCBuffer; its in-place Scan!/Exscan! forms reference the undefined

@@ -83,6 +83,8 @@ PROTOTYPES = {
     "mpigx_allreduce": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mpigx_scan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mpigx_exscan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mpigx_reduce_scatter_block": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mpigx_reduce_scatter": (c_int, [c_void_p, c_void_p, _IP, c_int, c_int, c_void_p]),
     "mpigx_reduce_local": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int]),
     "mpigx_reduce_local_multi": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p, c_longlong, c_int, c_int, c_int,
                                          c_void_p]),

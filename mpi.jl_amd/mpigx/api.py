@@ -1089,6 +1089,68 @@ def Allreduce(sendbuf, op, comm):
     return _item(out)
 
 
+def Reduce_scatter_block_(*args):
+    """Reduce_scatter_block!(sendbuf, recvbuf, count, op, comm)  count = elements per block
+    Reduce_scatter_block!(sendbuf, recvbuf, op, comm)         (count = length(recvbuf))
+    Reduce_scatter_block!(buf, count, op, comm)  (IN_PLACE: size * count elements in `buf`,
+    the result in its first `count`)
+    MPI_Reduce_scatter_block; MPI.jl v0.14.2 has no wrapper of this name."""
+    if len(args) == 4 and not _is_array(args[1]) and not isinstance(args[1], Buffer):
+        buf, count, op, comm = args
+        sendbuf, recvbuf = IN_PLACE, buf
+    elif len(args) == 4:
+        sendbuf, recvbuf, op, comm = args
+        count = _len(recvbuf)
+    else:
+        sendbuf, recvbuf, count, op, comm = args
+    count = _cint(count)
+    total = _cint(count * Comm_size(comm))
+    if sendbuf is IN_PLACE:
+        _assert_minlength(recvbuf, total)
+    else:
+        _assert_minlength(sendbuf, total)
+        _assert_minlength(recvbuf, count)
+        assert _eltype(sendbuf) == _eltype(recvbuf)
+    T = _eltype(recvbuf)
+    opx = _as_op(op, _dtype(recvbuf))
+    _call("Reduce_scatter_block", recvbuf, comm, _ptr(sendbuf), _ptr(recvbuf), count, T.val, _op_val(opx, recvbuf))
+    return recvbuf
+
+
+def Reduce_scatter_block(sendbuf, op, comm):
+    """Allocating form: `sendbuf` holds size blocks of length(sendbuf) / size
+    elements; returns this rank's reduced block."""
+    n = Comm_size(comm)
+    total = _len(sendbuf)
+    if total % n:
+        raise ValueError(f"Reduce_scatter_block: {total} elements do not divide into {n} blocks")
+    return Reduce_scatter_block_(sendbuf, _empty_like(sendbuf, total // n), total // n, op, comm)
+
+
+def Reduce_scatter_(*args):
+    """Reduce_scatter!(sendbuf, recvbuf, counts, op, comm) / Reduce_scatter!(buf, counts, op, comm)
+    (IN_PLACE: sum(counts) elements in `buf`, the result in its first counts[rank])
+    MPI_Reduce_scatter; `counts` as in Allgatherv!."""
+    if len(args) == 4:
+        sendbuf, (recvbuf, counts, op, comm) = IN_PLACE, args
+    else:
+        sendbuf, recvbuf, counts, op, comm = args
+    cc = _cints([_cint(x) for x in counts])
+    total = _cint(sum(int(x) for x in counts))
+    mine = int(counts[Comm_rank(comm)])
+    assert recvbuf is not None
+    if sendbuf is IN_PLACE:
+        _assert_minlength(recvbuf, total)
+    else:
+        _assert_minlength(sendbuf, total)
+        _assert_minlength(recvbuf, mine)
+        assert _eltype(sendbuf) == _eltype(recvbuf)
+    T = _eltype(recvbuf)
+    opx = _as_op(op, _dtype(recvbuf))
+    _call("Reduce_scatter", recvbuf, comm, _ptr(sendbuf), _ptr(recvbuf), cc, T.val, _op_val(opx, recvbuf))
+    return recvbuf
+
+
 def _scan_dispatch(args):
     """Scan!/Exscan!(sendbuf, recvbuf, count, op, comm) | (sendbuf, recvbuf, op, comm)
     | in-place (buf, count, op, comm) | (buf, op, comm).  (collective.jl:760-783 /

@@ -254,6 +254,13 @@ int mpigx_alltoall(const void *sendbuf, int sendcount, int sendtype, void *recvb
                    int recvcount, int recvtype, mpigx_comm_t comm);
 /* v-collectives and rooted variants.  counts/displs are
  * host int arrays in elements, as MPI.jl passes them (Ptr{Cint}).
+ * Gatherv / Scatterv / Allgatherv / Alltoallv take any committed datatype on
+ * either side (padded structs, resized vectors whose instances interleave,
+ * subarrays ...): counts and displacements are in units of that side's
+ * extent, the two sides may differ in type as long as each pair's packed
+ * byte counts agree, and bytes of a receive buffer outside the type map keep
+ * their contents.  A non-contiguous side is packed / unpacked on device in one
+ * launch (seg_pack_kernel); predefined and contiguous types move as before.
  * MPI_Gather   — collective.jl:230-246 (sendbuf IN_PLACE at root) */
 int mpigx_gather(const void *sendbuf, int sendcount, int sendtype, void *recvbuf, int recvcount,
                  int recvtype, int root, mpigx_comm_t comm);
@@ -449,12 +456,22 @@ int mpigx_win_lock(int lock_type, int rank, int assert_, mpigx_win_t win);
 int mpigx_win_unlock(int rank, mpigx_win_t win);
 /* MPI_Win_get_attr(MPI_WIN_CREATE_FLAVOR) analogue */
 int mpigx_win_get_flavor(mpigx_win_t win, int *flavor);
-/* MPI_Get / MPI_Put — onesided.jl:150-184 */
+/* MPI_Get / MPI_Put — onesided.jl:150-184.  Origin and target datatype may be
+ * any committed types, also different ones, describing the same number of
+ * packed bytes (else MPI_ERR_TYPE); the window bounds are checked against the
+ * target type's true bounds over target_count instances (MPI_ERR_RMA_RANGE).
+ * Get pulls typed -> typed in one pass.  Put sends the target type's
+ * flattened runs with the envelope: at most 64 runs, a type with more is
+ * refused with MPI_ERR_TYPE before anything is posted. */
 int mpigx_get(void *origin_addr, int origin_count, int origin_datatype, int target_rank,
               long long target_disp, int target_count, int target_datatype, mpigx_win_t win);
 int mpigx_put(const void *origin_addr, int origin_count, int origin_datatype, int target_rank,
               long long target_disp, int target_count, int target_datatype, mpigx_win_t win);
-/* MPI_Fetch_and_op — onesided.jl:186-195 */
+/* MPI_Fetch_and_op / MPI_Accumulate / MPI_Get_accumulate take predefined
+ * types and derived types that are a contiguous run of ONE predefined type
+ * (reduced element-wise, as in the reductions); any other derived type is
+ * MPI_ERR_TYPE there — a deliberate limit.
+ * MPI_Fetch_and_op — onesided.jl:186-195 */
 int mpigx_fetch_and_op(const void *origin_addr, void *result_addr, int datatype, int target_rank,
                        long long target_disp, int op, mpigx_win_t win);
 /* MPI_Accumulate — onesided.jl:197-206 */
@@ -474,10 +491,12 @@ int mpigx_get_accumulate(const void *origin_addr, int origin_count, int origin_d
  * MPI_ERR_TYPE, not aliased), usable
  * wherever a datatype is taken once committed — point-to-point (strided and
  * dense SubArrays, buffers.jl:104-117; padded isbits structs,
- * datatypes.jl:269-316) and the byte-moving collectives (Bcast, Allgather,
- * Alltoall, Gather, Scatter), which pack non-contiguous types on device
- * (pack_kernel) around the contiguous algorithm.  Reductions accept derived
- * types that are contiguous runs of one predefined type.  lb / extent /
+ * datatypes.jl:269-316), the byte-moving collectives (Bcast, Allgather,
+ * Alltoall, Gather, Scatter and the v-collectives), which pack non-contiguous
+ * types on device (pack_kernel, seg_pack_kernel) around the contiguous
+ * algorithm, and one-sided Get / Put (typed_xfer_kernel).  Reductions and the
+ * accumulate family accept derived types that are contiguous runs of one
+ * predefined type.  lb / extent /
  * sizes follow MPICH 3.3.2 (tests/golden/types_golden.json). */
 #define MPIGX_ORDER_C 56
 #define MPIGX_ORDER_FORTRAN 57

@@ -65,6 +65,14 @@ int mpigx_read_probe(const void *const *in, int nin, long long bytes, void *sink
  * no arithmetic to speak of: the box's ceiling for that kernel
  * (roofline.peak_measured in bench.py).  Asynchronous on `stream`. */
 int mpigx_mix_probe(const void *const *in, int nin, long long bytes, void *out, void *stream);
+/* The v-collectives' segmented pack / unpack on its own (copy.hip
+ * seg_pack_kernel), so that its index arithmetic can be checked in one
+ * process: segment j = counts[j] instances of `datatype` whose first lies at
+ * typed + displs[j] * extent, packed at packed + offsets[j] (unpack != 0: the
+ * reverse); nseg <= MPIGX_MAX_RANKS, one launch on `stream`, blocking. */
+int mpigx_pack_segments(const void *typed, int datatype, int nseg, const long long *counts,
+                        const long long *displs, const long long *offsets, void *packed, int unpack,
+                        void *stream);
 /* Zero-copy paths (user buffers mapped by the peers over IPC): how many
  * launches ran on a cached view without any host exchange, and how many
  * host exchanges of buffer registrations there were.  Diagnostic. */

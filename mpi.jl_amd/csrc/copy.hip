@@ -4,6 +4,7 @@
 // xGMI with all peers interleaved per thread (block_gather).
 #include "kernels.hpp"
 #include "launch.hpp"
+#include "typed.hpp"
 
 namespace mpigx {
 
@@ -502,6 +503,140 @@ hipError_t launch_pack(hipStream_t s, const PackArgs& a) {
     case 4: hipLaunchKernelGGL(pack_kernel<4>, dim3((unsigned)g), dim3(kThreads), 0, s, a); break;
     case 2: hipLaunchKernelGGL(pack_kernel<2>, dim3((unsigned)g), dim3(kThreads), 0, s, a); break;
     default: hipLaunchKernelGGL(pack_kernel<1>, dim3((unsigned)g), dim3(kThreads), 0, s, a); break;
+  }
+  return hipGetLastError();
+}
+
+// Packed byte p of a stream of instances of one type -> byte offset from the
+// typed buffer's pointer (pack_kernel's map: instance, run by binary search
+// over the per-instance prefix, block, byte).  nruns = 0: contiguous.
+__device__ __forceinline__ long long typed_off(const TypeRun* runs, const long long* pfx, int nruns, long long size,
+                                               long long extent, long long p) {
+  if (nruns == 0) return p;
+  const long long k = p / size, r = p - k * size;
+  int lo = 0;
+  if (nruns > 1) {
+    int hi = nruns - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (pfx[mid] <= r) lo = mid;
+      else hi = mid - 1;
+    }
+  }
+  const TypeRun R = runs[lo];
+  const long long q = r - pfx[lo], i = q / R.len, b = q - i * R.len;
+  return k * extent + R.off + i * R.stride + b;
+}
+
+template <int W>
+struct UnitOf {
+  using type = typename std::conditional<W == 16, u32x4,
+               typename std::conditional<W == 8, uint64_t,
+               typename std::conditional<W == 4, uint32_t,
+               typename std::conditional<W == 2, uint16_t, uint8_t>::type>::type>::type>::type;
+};
+
+// Segmented pack / unpack (typed.hpp SegPackArgs): every range of a
+// v-collective's typed side in one launch.  Block b serves segment j with
+// blk0[j] <= b < blk0[j+1] and, of that segment's units, the share
+// [k*share, (k+1)*share) of its k-th block.
+template <int W>
+__global__ __launch_bounds__(kThreads) void seg_pack_kernel(SegPackArgs A) {
+  pull_acquire(A.coherent);
+  using V = typename UnitOf<W>::type;
+  const int b = blockIdx.x;
+  int j = 0;
+  while (j + 1 < A.nseg && b >= A.blk0[j + 1]) ++j;
+  const long long g = A.blk0[j + 1] - A.blk0[j], k = b - A.blk0[j];
+  const long long share = (A.units[j] + g - 1) / g;
+  const long long u0 = lmin(k * share, A.units[j]), u1 = lmin(u0 + share, A.units[j]);
+  char* typed = A.typed + A.t_off[j];
+  char* contig = A.contig + A.c_off[j];
+  for (long long u = u0 + threadIdx.x; u < u1; u += blockDim.x) {
+    const long long p = u * W;
+    const long long t = typed_off(A.runs, A.pfx, A.nruns, A.size, A.extent, p);
+    if (A.unpack) *reinterpret_cast<V*>(typed + t) = *reinterpret_cast<const V*>(contig + p);
+    else *reinterpret_cast<V*>(contig + p) = *reinterpret_cast<const V*>(typed + t);
+  }
+  pull_release(A.coherent);
+}
+
+// Deals kSegGrid blocks to the non-empty segments in proportion to their
+// units (at least one each; an empty segment gets none) and launches; nothing
+// is launched when every segment is empty.
+hipError_t launch_seg_pack(hipStream_t s, const SegPackArgs& in) {
+  SegPackArgs a = in;
+  long long total = 0;
+  for (int j = 0; j < a.nseg; ++j) total += a.units[j];
+  if (total <= 0) return hipSuccess;
+  long long G = (total + kThreads - 1) / kThreads;
+  G = G > kSegGrid ? kSegGrid : G;
+  a.blk0[0] = 0;
+  for (int j = 0; j < a.nseg; ++j) {
+    long long g = 0;
+    if (a.units[j] > 0) {
+      g = (long long)((double)G * (double)a.units[j] / (double)total);
+      const long long need = (a.units[j] + kThreads - 1) / kThreads;
+      g = g > need ? need : g;
+      g = g < 1 ? 1 : g;
+    }
+    a.blk0[j + 1] = a.blk0[j] + (int)g;
+  }
+  for (int j = a.nseg; j < kMaxRanks; ++j) a.blk0[j + 1] = a.blk0[a.nseg];
+  const dim3 grid((unsigned)a.blk0[a.nseg]);
+  switch (a.w) {
+    case 16: hipLaunchKernelGGL(seg_pack_kernel<16>, grid, dim3(kThreads), 0, s, a); break;
+    case 8: hipLaunchKernelGGL(seg_pack_kernel<8>, grid, dim3(kThreads), 0, s, a); break;
+    case 4: hipLaunchKernelGGL(seg_pack_kernel<4>, grid, dim3(kThreads), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(seg_pack_kernel<2>, grid, dim3(kThreads), 0, s, a); break;
+    default: hipLaunchKernelGGL(seg_pack_kernel<1>, grid, dim3(kThreads), 0, s, a); break;
+  }
+  return hipGetLastError();
+}
+
+// Typed -> typed transfer (typed.hpp TypedXferArgs): unit u of the packed
+// stream is read at src through the source map and written at dst through the
+// destination map, one pass.  The destination is always local memory; the
+// source may be a peer's (IPC-mapped) buffer, hence xfer_kernel's bracket.
+template <int W>
+__global__ __launch_bounds__(kThreads) void typed_xfer_kernel(TypedXferArgs A) {
+  // run lists that arrived as arguments are searched with per-lane indices:
+  // staged in LDS (kernel arguments indexed at run time would go to scratch)
+  __shared__ TypeRun sruns[kInlineRuns];
+  __shared__ long long spfx[kInlineRuns + 1];
+  if (A.s.inl | A.d.inl) {
+    for (int i = threadIdx.x; i < kInlineRuns; i += blockDim.x) sruns[i] = A.iruns[i];
+    for (int i = threadIdx.x; i <= kInlineRuns; i += blockDim.x) spfx[i] = A.ipfx[i];
+    __syncthreads();
+  }
+  pull_acquire(A.coherent);
+  using V = typename UnitOf<W>::type;
+  const TypeRun* sr = A.s.inl ? sruns : A.s.runs;
+  const long long* sp = A.s.inl ? spfx : A.s.pfx;
+  const TypeRun* dr = A.d.inl ? sruns : A.d.runs;
+  const long long* dp = A.d.inl ? spfx : A.d.pfx;
+  const long long nt = (long long)gridDim.x * blockDim.x;
+  for (long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x; u < A.units; u += nt) {
+    const long long p = u * W;
+    const long long so = typed_off(sr, sp, A.s.nruns, A.s.size, A.s.extent, p);
+    const long long dO = typed_off(dr, dp, A.d.nruns, A.d.size, A.d.extent, p);
+    *reinterpret_cast<V*>(A.dst + dO) = *reinterpret_cast<const V*>(A.src + so);
+  }
+  pull_release(A.coherent);
+}
+
+hipError_t launch_typed_xfer(hipStream_t s, const TypedXferArgs& a) {
+  if (a.units <= 0) return hipSuccess;
+  if (a.s.inl && a.d.inl) return hipErrorInvalidValue;  // one inline run list per launch
+  long long g = (a.units + kThreads - 1) / kThreads;
+  g = g > kSegGrid ? kSegGrid : g;
+  const dim3 grid((unsigned)g);
+  switch (a.w) {
+    case 16: hipLaunchKernelGGL(typed_xfer_kernel<16>, grid, dim3(kThreads), 0, s, a); break;
+    case 8: hipLaunchKernelGGL(typed_xfer_kernel<8>, grid, dim3(kThreads), 0, s, a); break;
+    case 4: hipLaunchKernelGGL(typed_xfer_kernel<4>, grid, dim3(kThreads), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(typed_xfer_kernel<2>, grid, dim3(kThreads), 0, s, a); break;
+    default: hipLaunchKernelGGL(typed_xfer_kernel<1>, grid, dim3(kThreads), 0, s, a); break;
   }
   return hipGetLastError();
 }

@@ -2070,6 +2070,8 @@ int vexchange(mpigx_comm* c, const VSpec& s) {
 namespace mpigx {
 namespace rt {
 int comm_check(mpigx_comm* c) { return check_comm(c); }
+char* tmp_alloc(mpigx_comm* c, long long bytes) { return tmp_get(c, bytes); }
+void tmp_release(mpigx_comm* c, char* p) { tmp_put(c, p, 0); }
 void comm_mark_broken(mpigx_comm* c) { mark_broken(c); }
 int dtype_size(int datatype) {
   const TypeInfo* t = find_type(datatype);
@@ -3469,8 +3471,10 @@ int mpigx_alltoall(const void* sendbuf, int sendcount, int sendtype, void* recvb
 // ---------------------------------------------------------------------------
 // v-collectives and rooted variants (collective.jl:90-578)
 // ---------------------------------------------------------------------------
-// Element size for the v-collectives: predefined types and contiguous derived
-// types (displacements are in extents, equal to sizes only then).
+// Element size for the v-collectives' byte path: predefined types and
+// contiguous derived types (displacements are in extents, equal to sizes only
+// then).  A call with any other committed type on a side that is read takes
+// the typed path below (needs_pack, *_typed) and never comes here.
 static int vsize(int dtype, int* out) {
   rt::TypeDesc d;
   if (rt::type_info(dtype, &d) || !d.contig || d.size > 0x7fffffff) return MPIGX_ERR_TYPE;
@@ -3484,6 +3488,220 @@ static int type_bytes(int dtype, long long count, long long* out) {
   if (count < 0) return MPIGX_ERR_COUNT;
   *out = count * sz;
   return MPIGX_SUCCESS;
+}
+
+// A committed derived type that is not `count * size` contiguous bytes: the
+// v-collectives send it through the typed path.
+static bool needs_pack(int dtype) {
+  rt::TypeDesc d;
+  return !rt::type_info(dtype, &d) && d.derived && !d.contig;
+}
+
+// One side of a v-collective in any committed datatype.  Counts and
+// displacements are in extents: instance j of block p lies at
+// user + (dsp[p] + j) * extent.  A contiguous type is addressed in place
+// (block p = len[p] bytes at off[p] = dsp[p] * size).  Any other type goes
+// through a pooled temporary in which block p's packed bytes start at the
+// 16-B-aligned prefix off[p], so that the byte-moving vexchange moves them
+// unchanged, and ONE seg_pack_kernel launch packs (before the exchange) or
+// unpacks (after it) every block.
+struct VSide {
+  mpigx_comm* c = nullptr;
+  rt::TypeDesc d{};
+  int type = 0, nseg = 0;
+  bool pack = false;
+  char* user = nullptr;  // the typed buffer
+  char* buf = nullptr;   // what vexchange addresses: user, or the temporary
+  char* tmp = nullptr;
+  long long cnt[kMaxRanks] = {}, dsp[kMaxRanks] = {}, off[kMaxRanks] = {}, len[kMaxRanks] = {};
+  ~VSide() {
+    if (tmp) tmp_put(c, tmp, 0);
+  }
+};
+
+// counts == NULL: one block of count1 instances at the pointer.
+static int vside_init(mpigx_comm* c, VSide* v, int type, const void* user, int nseg, const int* counts,
+                      const int* displs, int count1) {
+  if (rt::type_info(type, &v->d)) return MPIGX_ERR_TYPE;
+  v->c = c;
+  v->type = type;
+  v->nseg = nseg;
+  v->user = (char*)user;
+  v->pack = v->d.derived && !v->d.contig;
+  long long total = 0;
+  for (int p = 0; p < nseg; ++p) {
+    v->cnt[p] = counts ? counts[p] : count1;
+    if (v->cnt[p] < 0) return MPIGX_ERR_COUNT;
+    v->dsp[p] = counts ? displs[p] : 0;
+    v->len[p] = v->cnt[p] * v->d.size;
+    v->off[p] = v->pack ? total : v->dsp[p] * v->d.size;
+    total += (v->len[p] + 15) & ~15ll;
+  }
+  v->buf = v->user;
+  if (total && !user) return MPIGX_ERR_BUFFER;
+  if (v->pack) {
+    if (!(v->tmp = tmp_get(c, total > 16 ? total : 16))) return MPIGX_ERR_NO_MEM;
+    v->buf = v->tmp;
+  }
+  return MPIGX_SUCCESS;
+}
+
+// Pack (unpack = 0) or unpack every block of a packed side on the comm's
+// stream; block `skip` (if >= 0) is left alone.
+static int vside_move(VSide* v, int unpack, int skip = -1) {
+  if (!v->pack) return MPIGX_SUCCESS;
+  long long cnt[kMaxRanks];
+  for (int p = 0; p < v->nseg; ++p) cnt[p] = p == skip ? 0 : v->cnt[p];
+  const int rc = rt::type_pack_seg(v->type, v->user, v->nseg, cnt, v->dsp, v->off, v->tmp, unpack, v->c->device,
+                                   v->c->stream);
+  if (!rc) v->c->unflagged = true;  // the final finish() drains the stream
+  return rc;
+}
+
+static int gatherv_typed(const void* send, int scount, int stype, void* recv, const int* rcounts, const int* displs,
+                         int rtype, int root, mpigx_comm_t c) {
+  int rc = check_comm(c);
+  if (rc) return rc;
+  const int n = c->n, r = c->rank;
+  if (root < 0 || root >= n) return MPIGX_ERR_ROOT;
+  const bool isroot = r == root, inplace = send == MPIGX_IN_PLACE;
+  if (inplace && !isroot) return MPIGX_ERR_BUFFER;
+  VSide S, R;
+  VSpec s;
+  if (isroot) {
+    if (!recv) return MPIGX_ERR_BUFFER;
+    if ((rc = vside_init(c, &R, rtype, recv, n, rcounts, displs, 0))) return rc;
+    for (int p = 0; p < n; ++p) {
+      s.p_len[p] = R.len[p];
+      s.p_slot[p] = 0;
+      s.p_dst[p] = R.off[p];
+    }
+    if (inplace) s.p_len[r] = 0;
+  }
+  if (!inplace) {
+    if ((rc = vside_init(c, &S, stype, send, 1, nullptr, nullptr, scount))) return rc;
+    s.ncopy = 1;
+    s.c_slot[0] = 0;
+    s.c_src[0] = S.off[0];
+    s.c_len[0] = S.len[0];
+  }
+  s.send = S.buf;
+  s.recv = R.buf;
+  rc = vside_move(&S, 0);
+  if (!rc) rc = vexchange(c, s);
+  if (!rc) rc = vside_move(&R, 1, inplace ? r : -1);
+  if (!rc) rc = finish(c);
+  return rc;
+}
+
+static int scatterv_typed(const void* send, const int* scounts, const int* displs, int stype, void* recv, int rcount,
+                          int rtype, int root, mpigx_comm_t c) {
+  int rc = check_comm(c);
+  if (rc) return rc;
+  const int n = c->n, r = c->rank;
+  if (root < 0 || root >= n) return MPIGX_ERR_ROOT;
+  const bool isroot = r == root, inplace = recv == MPIGX_IN_PLACE;
+  if (inplace && !isroot) return MPIGX_ERR_BUFFER;
+  VSide S, R;
+  VSpec s;
+  if (isroot) {
+    if (!send) return MPIGX_ERR_BUFFER;
+    if ((rc = vside_init(c, &S, stype, send, n, scounts, displs, 0))) return rc;
+    s.ncopy = n;
+    for (int q = 0; q < n; ++q) {
+      s.c_slot[q] = q;
+      s.c_src[q] = S.off[q];
+      s.c_len[q] = (inplace && q == r) ? 0 : S.len[q];
+    }
+  }
+  if (!inplace) {
+    if ((rc = vside_init(c, &R, rtype, recv, 1, nullptr, nullptr, rcount))) return rc;
+    s.p_len[root] = R.len[0];
+    s.p_slot[root] = r;
+    s.p_dst[root] = R.off[0];
+  }
+  s.send = S.buf;
+  s.recv = R.buf;
+  rc = vside_move(&S, 0, inplace ? r : -1);
+  if (!rc) rc = vexchange(c, s);
+  if (!rc) rc = vside_move(&R, 1);
+  if (!rc) rc = finish(c);
+  return rc;
+}
+
+static int allgatherv_typed(const void* send, int scount, int stype, void* recv, const int* rcounts,
+                            const int* displs, int rtype, mpigx_comm_t c) {
+  int rc = check_comm(c);
+  if (rc) return rc;
+  if (!rcounts || !displs) return MPIGX_ERR_ARG;
+  const int n = c->n, r = c->rank;
+  const bool inplace = send == MPIGX_IN_PLACE;
+  VSide S, R;
+  VSpec s;
+  if ((rc = vside_init(c, &R, rtype, recv, n, rcounts, displs, 0))) return rc;
+  for (int p = 0; p < n; ++p) {
+    s.p_len[p] = R.len[p];
+    s.p_slot[p] = 0;
+    s.p_dst[p] = R.off[p];
+  }
+  s.ncopy = 1;
+  s.c_slot[0] = 0;
+  if (inplace) {  // my contribution is block r of the receive side (packed first if the type needs it)
+    long long mine[kMaxRanks] = {};
+    mine[r] = R.cnt[r];
+    if (R.pack) {
+      rc = rt::type_pack_seg(rtype, R.user, n, mine, R.dsp, R.off, R.tmp, 0, c->device, c->stream);
+      if (rc) return rc;
+      c->unflagged = true;
+    }
+    s.send = R.buf;
+    s.c_src[0] = R.off[r];
+    s.c_len[0] = R.len[r];
+    s.p_len[r] = 0;
+  } else {
+    if ((rc = vside_init(c, &S, stype, send, 1, nullptr, nullptr, scount))) return rc;
+    s.send = S.buf;
+    s.c_src[0] = S.off[0];
+    s.c_len[0] = S.len[0];
+    if ((rc = vside_move(&S, 0))) return rc;
+  }
+  s.recv = R.buf;
+  rc = vexchange(c, s);
+  if (!rc) rc = vside_move(&R, 1, inplace ? r : -1);
+  if (!rc) rc = finish(c);
+  return rc;
+}
+
+static int alltoallv_typed(const void* send, const int* scounts, const int* sdispls, int stype, void* recv,
+                           const int* rcounts, const int* rdispls, int rtype, mpigx_comm_t c) {
+  int rc = check_comm(c);
+  if (rc) return rc;
+  if (!rcounts || !rdispls) return MPIGX_ERR_ARG;
+  const int n = c->n, r = c->rank;
+  const bool inplace = send == MPIGX_IN_PLACE;
+  if (!inplace && (!scounts || !sdispls)) return MPIGX_ERR_ARG;
+  VSide S, R;
+  VSpec s;
+  if ((rc = vside_init(c, &R, rtype, recv, n, rcounts, rdispls, 0))) return rc;
+  if (!inplace && (rc = vside_init(c, &S, stype, send, n, scounts, sdispls, 0))) return rc;
+  // MPI-2.2 IN_PLACE: the send layout is the receive layout
+  VSide& O = inplace ? R : S;
+  s.ncopy = n;
+  for (int q = 0; q < n; ++q) {
+    s.c_slot[q] = q;
+    s.c_src[q] = O.off[q];
+    s.c_len[q] = O.len[q];
+    s.p_len[q] = R.len[q];
+    s.p_slot[q] = r;
+    s.p_dst[q] = R.off[q];
+  }
+  s.send = O.buf;
+  s.recv = R.buf;
+  rc = vside_move(&O, 0);
+  if (!rc) rc = vexchange(c, s);
+  if (!rc) rc = vside_move(&R, 1);
+  if (!rc) rc = finish(c);
+  return rc;
 }
 
 // MPI_Gather / MPI_Gatherv (collective.jl:230-246, 363-382).  counts/displs
@@ -3566,6 +3784,8 @@ int mpigx_gather(const void* sendbuf, int sendcount, int sendtype, void* recvbuf
 int mpigx_gatherv(const void* sendbuf, int sendcount, int sendtype, void* recvbuf, const int* recvcounts,
                   const int* displs, int recvtype, int root, mpigx_comm_t c) {
   if (c && c->rank == root && (!recvcounts || !displs)) return MPIGX_ERR_ARG;
+  if (c && ((sendbuf != MPIGX_IN_PLACE && needs_pack(sendtype)) || (c->rank == root && needs_pack(recvtype))))
+    return gatherv_typed(sendbuf, sendcount, sendtype, recvbuf, recvcounts, displs, recvtype, root, c);
   return gather_common(sendbuf, sendcount, sendtype, recvbuf, 0, recvcounts, displs, recvtype, root, c);
 }
 
@@ -3643,12 +3863,16 @@ int mpigx_scatter(const void* sendbuf, int sendcount, int sendtype, void* recvbu
 int mpigx_scatterv(const void* sendbuf, const int* sendcounts, const int* displs, int sendtype, void* recvbuf,
                    int recvcount, int recvtype, int root, mpigx_comm_t c) {
   if (c && c->rank == root && (!sendcounts || !displs)) return MPIGX_ERR_ARG;
+  if (c && ((recvbuf != MPIGX_IN_PLACE && needs_pack(recvtype)) || (c->rank == root && needs_pack(sendtype))))
+    return scatterv_typed(sendbuf, sendcounts, displs, sendtype, recvbuf, recvcount, recvtype, root, c);
   return scatter_common(sendbuf, 0, sendcounts, displs, sendtype, recvbuf, recvcount, recvtype, root, c);
 }
 
 // MPI_Allgatherv (collective.jl:424-437)
 int mpigx_allgatherv(const void* sendbuf, int sendcount, int sendtype, void* recvbuf, const int* recvcounts,
                      const int* displs, int recvtype, mpigx_comm_t c) {
+  if (needs_pack(recvtype) || (sendbuf != MPIGX_IN_PLACE && needs_pack(sendtype)))
+    return allgatherv_typed(sendbuf, sendcount, sendtype, recvbuf, recvcounts, displs, recvtype, c);
   int rc = check_comm(c);
   if (rc) return rc;
   if (!recvcounts || !displs) return MPIGX_ERR_ARG;
@@ -3687,6 +3911,8 @@ int mpigx_allgatherv(const void* sendbuf, int sendcount, int sendtype, void* rec
 // layout from recvcounts/rdispls.
 int mpigx_alltoallv(const void* sendbuf, const int* sendcounts, const int* sdispls, int sendtype, void* recvbuf,
                     const int* recvcounts, const int* rdispls, int recvtype, mpigx_comm_t c) {
+  if (needs_pack(recvtype) || (sendbuf != MPIGX_IN_PLACE && needs_pack(sendtype)))
+    return alltoallv_typed(sendbuf, sendcounts, sdispls, sendtype, recvbuf, recvcounts, rdispls, recvtype, c);
   int rc = check_comm(c);
   if (rc) return rc;
   if (!recvcounts || !rdispls) return MPIGX_ERR_ARG;

@@ -45,7 +45,9 @@ using namespace mpigx;
 
 namespace {
 
-enum RmaKind { RK_PUT = 1, RK_ACC = 2, RK_GACC = 3 };
+// RK_PUTT: Put through a derived target type (runtime.hpp RmaType): count =
+// packed bytes, rep = the origin's table entry, res_off = target instances
+enum RmaKind { RK_PUT = 1, RK_ACC = 2, RK_GACC = 3, RK_PUTT = 4 };
 
 AccLauncher acc_launcher(int rep) {
   switch (rep) {
@@ -94,6 +96,21 @@ struct mpigx_win {
   uint64_t rseq[kMaxRanks] = {};  // target: envelopes applied per origin
   int lock_held[kMaxRanks] = {};  // 0 none, 1 shared, 2 exclusive, 3 NOCHECK
   bool gets_pending = false;
+  // origin side of typed Puts: which envelope last named each of my type-table
+  // entries, and the packed origin temporaries that live until their
+  // envelope is done
+  struct TypeUse {
+    bool busy = false;
+    int t = 0;
+    uint64_t seq = 0;
+  };
+  TypeUse tt_use[kRmaTypeSlots];
+  struct PutTmp {
+    char* p;
+    int t;
+    uint64_t seq;
+  };
+  std::vector<PutTmp> put_tmps;
   bool ready = false;  // every rank reset its rows of the slot (first exchange done)
   int err = MPIGX_SUCCESS;        // first deferred (target-side) error
   struct Attach {
@@ -176,27 +193,55 @@ struct Deadline {
 // ---------------------------------------------------------------------------
 // My window memory for [disp, disp+bytes) (disp: byte offset, or the absolute
 // address for dynamic windows); null if out of range.
-char* local_target(mpigx_win* w, long long disp, long long bytes) {
+// A typed access touches [disp + lo, disp + lo + bytes) (the type's true
+// bounds); the pointer returned is the one for disp itself.
+char* local_target(mpigx_win* w, long long disp, long long bytes, long long lo = 0) {
   if (w->flavor == MPIGX_WIN_FLAVOR_DYNAMIC) {
-    const uintptr_t a = (uintptr_t)disp;
+    const uintptr_t a = (uintptr_t)(disp + lo);
     for (auto& r : w->attached)
-      if (a >= (uintptr_t)r.base && a + bytes <= (uintptr_t)r.base + r.size) return (char*)a;
+      if (a >= (uintptr_t)r.base && a + bytes <= (uintptr_t)r.base + r.size) return (char*)(uintptr_t)disp;
     return nullptr;
   }
-  if (disp < 0 || disp + bytes > w->size) return nullptr;
+  if (disp < 0 || disp + lo < 0 || disp + lo + bytes > w->size) return nullptr;
   return w->base + disp;
+}
+
+// True bounds of `count` instances of a flattened type, from the pointer.
+void flat_span(const RmaType& T, long long count, long long* lo, long long* hi) {
+  long long l = 0, h = 0;
+  for (int i = 0; i < T.nruns; ++i) {
+    const TypeRun& r = T.runs[i];
+    const long long last = r.n > 1 ? (r.n - 1) * r.stride : 0;
+    const long long rl = r.off + std::min(0ll, last), rh = r.off + std::max(0ll, last) + r.len;
+    l = i ? std::min(l, rl) : rl;
+    h = i ? std::max(h, rh) : rh;
+  }
+  const long long step = count > 0 ? (count - 1) * T.extent : 0;
+  *lo = l + std::min(0ll, step);
+  *hi = h + std::max(0ll, step);
 }
 
 int apply_one(mpigx_win* w, int o, RmaEnvelope* e, hipStream_t ws) {
   mpigx_comm* c = w->c;
   int rep = e->rep, esize = 1;
-  if (e->kind != RK_PUT) {
+  if (e->kind != RK_PUT && e->kind != RK_PUTT) {
     static const int kSize[R_COUNT] = {1, 1, 2, 2, 4, 4, 8, 8, 4, 8, 8, 16, 2};
     if (rep < 0 || rep >= R_COUNT) return MPIGX_ERR_TYPE;
     esize = kSize[rep];
   }
   const long long bytes = e->count * esize;
-  char* dst = local_target(w, e->tdisp, bytes);
+  const RmaType* T = nullptr;
+  char* dst;
+  if (e->kind == RK_PUTT) {
+    if (rep < 0 || rep >= kRmaTypeSlots) return MPIGX_ERR_INTERN;
+    T = &wshm(w)->ttab[o][rep];
+    if (T->nruns < 1 || T->nruns > kRmaRunCap || T->size <= 0 || e->res_off * T->size != bytes) return MPIGX_ERR_TYPE;
+    long long lo, hi;
+    flat_span(*T, e->res_off, &lo, &hi);
+    dst = local_target(w, e->tdisp, hi - lo, lo);
+  } else {
+    dst = local_target(w, e->tdisp, bytes);
+  }
   if (!dst) return MPIGX_ERR_RMA_RANGE;
   const char* src;
   if (same_process(c, o)) {
@@ -208,6 +253,7 @@ int apply_one(mpigx_win* w, int o, RmaEnvelope* e, hipStream_t ws) {
     if (!b) return MPIGX_ERR_INTERN;
     src = b + e->off;
   }
+  if (e->kind == RK_PUTT) return rt::flat_xfer(*T, dst, src, bytes, ws);
   if (e->kind == RK_PUT) {
     XferArgs a;
     memset(&a, 0, sizeof a);
@@ -287,7 +333,7 @@ int post(mpigx_win* w, int t, int kind, int op, int rep, long long tdisp, long l
   RmaEnvelope tmp;
   memset((void*)&tmp, 0, sizeof tmp);
   tmp.raw = (unsigned long long)(uintptr_t)origin;
-  const bool needs_src = !(kind != RK_PUT && op == O_NOOP);
+  const bool needs_src = !(kind != RK_PUT && kind != RK_PUTT && op == O_NOOP);
   if (needs_src && !same_process(c, t) &&
       !rt::export_buf(c, origin, &tmp.buf_id, &tmp.off, &tmp.h))
     return MPIGX_ERR_BUFFER;
@@ -379,15 +425,17 @@ int sync_stream(mpigx_comm* c) {
 }
 
 // The target's memory for [disp, disp+bytes) as mapped in this process (Get).
-const char* remote_target(mpigx_win* w, int t, long long disp, long long bytes) {
+// A typed access touches [lo, lo + bytes) from the displacement (the type's
+// true bounds); the pointer returned is the one for the displacement itself.
+const char* remote_target(mpigx_win* w, int t, long long disp, long long bytes, long long lo = 0) {
   mpigx_comm* c = w->c;
   if (w->flavor != MPIGX_WIN_FLAVOR_DYNAMIC) {
     const long long off = disp * w->peer_du[t];
-    if (disp < 0 || off + bytes > w->peer_size[t] || !w->peer_base[t]) return nullptr;
+    if (disp < 0 || off + lo < 0 || off + lo + bytes > w->peer_size[t] || !w->peer_base[t]) return nullptr;
     return w->peer_base[t] + off;
   }
-  const unsigned long long a = (unsigned long long)disp;
-  if (t == c->rank) return local_target(w, disp, bytes);
+  if (t == c->rank) return local_target(w, disp, bytes, lo);
+  const unsigned long long a = (unsigned long long)(disp + lo);
   WinShm* S = wshm(w);
   for (int k = 0; k < kMaxAttach; ++k) {
     DynRegion& r = S->dyn[t][k];
@@ -398,10 +446,10 @@ const char* remote_target(mpigx_win* w, int t, long long disp, long long bytes) 
     const hipIpcMemHandle_t h = r.h;
     if (r.gen.load(std::memory_order_acquire) != g) continue;  // rewritten meanwhile
     if (a < ra || a + bytes > ra + rs) continue;
-    if (same_process(c, t)) return (const char*)(uintptr_t)a;
+    if (same_process(c, t)) return (const char*)(uintptr_t)disp;
     char* b = rt::import_buf(c, t, id, h);
     if (!b) return nullptr;
-    return b + off + (a - ra);
+    return b + off + (long long)(a - ra) - lo;
   }
   return nullptr;
 }
@@ -449,15 +497,70 @@ int check_target(mpigx_win* w, int t) {
   return MPIGX_SUCCESS;
 }
 
-// Common argument checks of the data-moving calls: predefined types only,
-// origin and target describing the same bytes.
-int check_xfer(int ocount, int otype, int tcount, int ttype, int* esize) {
+// Common argument checks of Get / Put: any committed datatypes, origin and
+// target describing the same number of packed bytes (*bytes).  *typed: a side
+// is a derived type that is not contiguous, so the transfer goes through the
+// type maps (typed_xfer_kernel); predefined and contiguous derived types move
+// as bytes (xfer_kernel), as they always did.
+int check_xfer(int ocount, int otype, int tcount, int ttype, long long* bytes, bool* typed) {
   if (ocount < 0 || tcount < 0) return MPIGX_ERR_COUNT;
-  const int os = rt::dtype_size(otype), ts = rt::dtype_size(ttype);
-  if (os < 0 || ts < 0) return MPIGX_ERR_TYPE;
-  if ((long long)os * ocount != (long long)ts * tcount) return MPIGX_ERR_TYPE;
-  *esize = os;
+  rt::TypeDesc od, td;
+  if (rt::type_info(otype, &od) || rt::type_info(ttype, &td)) return MPIGX_ERR_TYPE;
+  if (od.size * ocount != td.size * tcount) return MPIGX_ERR_TYPE;
+  *bytes = od.size * ocount;
+  *typed = (od.derived && !od.contig) || (td.derived && !td.contig);
   return MPIGX_SUCCESS;
+}
+
+// Accumulate / Get_accumulate / Fetch_and_op take a derived type only if it is
+// a contiguous run of ONE predefined type, lowered to that type (as the
+// reductions do, mpigx.cpp lower_reduce_type); any other derived type is
+// MPI_ERR_TYPE.
+int lower_acc_type(int* datatype, int* count) {
+  if (rt::dtype_size(*datatype) >= 0) return MPIGX_SUCCESS;
+  rt::TypeDesc d;
+  if (rt::type_info(*datatype, &d)) return MPIGX_ERR_TYPE;
+  const int bs = rt::dtype_size(d.basic);
+  if (!d.contig || d.basic == 0 || bs <= 0 || d.size % bs) return MPIGX_ERR_TYPE;
+  const long long n = (long long)*count * (d.size / bs);
+  if (n > 0x7fffffff) return MPIGX_ERR_COUNT;
+  *datatype = d.basic;
+  *count = (int)n;
+  return MPIGX_SUCCESS;
+}
+
+// Typed Puts: give back the packed origin temporaries whose envelope is done.
+void reclaim_put_tmps(mpigx_win* w, bool all) {
+  auto& v = w->put_tmps;
+  for (size_t i = 0; i < v.size();) {
+    RmaEnvelope* e = &wshm(w)->box[w->c->rank][v[i].t].slot[v[i].seq % kRmaSlots];
+    if (all || e->done.load(std::memory_order_acquire) >= v[i].seq + 1) {
+      rt::tmp_release(w->c, v[i].p);
+      v.erase(v.begin() + i);
+    } else {
+      ++i;
+    }
+  }
+}
+
+// An entry of my row of the window's type table that no pending envelope names.
+int claim_type_entry(mpigx_win* w, int* out) {
+  Deadline d(w->c);
+  for (;;) {
+    for (int k = 0; k < kRmaTypeSlots; ++k) {
+      mpigx_win::TypeUse& u = w->tt_use[k];
+      if (u.busy) {
+        RmaEnvelope* e = &wshm(w)->box[w->c->rank][u.t].slot[u.seq % kRmaSlots];
+        if (e->done.load(std::memory_order_acquire) >= u.seq + 1) u.busy = false;
+      }
+      if (!u.busy) {
+        *out = k;
+        return MPIGX_SUCCESS;
+      }
+    }
+    int rc = spin_progress(w, d);
+    if (rc) return rc;
+  }
 }
 
 struct WinBlob {
@@ -739,6 +842,7 @@ int mpigx_win_free(mpigx_win_t* pw) {
   rt::rma_progress(c);
   (void)hipStreamSynchronize(c->rma->ws);
   if (!rc) rc = take_err(w);
+  reclaim_put_tmps(w, true);
   free_local(w);
   *pw = nullptr;
   return rc;
@@ -890,18 +994,80 @@ int mpigx_get(void* origin_addr, int origin_count, int origin_datatype, int targ
   std::lock_guard<rt::BigLock> big(rt::big_lock());  // THREAD_MULTIPLE (runtime.hpp)
   int rc = check_win(w);
   if (rc) return rc;
-  int es;
-  rc = check_xfer(origin_count, origin_datatype, target_count, target_datatype, &es);
+  long long bytes;
+  bool typed;
+  rc = check_xfer(origin_count, origin_datatype, target_count, target_datatype, &bytes, &typed);
   if (rc) return rc;
   rc = check_target(w, target_rank);
   if (rc < 0) return MPIGX_SUCCESS;
   if (rc) return rc;
-  const long long bytes = (long long)origin_count * es;
   if (bytes == 0) return MPIGX_SUCCESS;
   if (!origin_addr) return MPIGX_ERR_BUFFER;
+  if (typed) {
+    // one pass over xGMI: the target's window through the target type into
+    // my buffer through the origin type; bounds = the target type's true bounds
+    long long lo, hi;
+    if ((rc = rt::type_span(target_datatype, target_count, &lo, &hi))) return rc;
+    const char* src = remote_target(w, target_rank, target_disp, hi - lo, lo);
+    if (!src) return MPIGX_ERR_RMA_RANGE;
+    if ((rc = order_after_stream(w->c))) return rc;
+    rc = rt::type_xfer(target_datatype, src, origin_datatype, origin_addr, bytes, w->c->device, w->c->rma->ws);
+    if (!rc) w->gets_pending = true;
+    return rc;
+  }
   const char* src = remote_target(w, target_rank, target_disp, bytes);
   if (!src) return MPIGX_ERR_RMA_RANGE;
   return pull(w, origin_addr, src, bytes);
+}
+
+// Put with a derived type on either side.  The origin packs a non-contiguous
+// origin buffer into a pooled temporary that lives until the envelope is done;
+// a non-contiguous target type travels as flattened runs in my row of the
+// window's type table (runtime.hpp RmaType) and the target scatters the
+// packed bytes through it into its own window (typed_xfer_kernel).  Every
+// refusal (run capacity, bounds) happens before anything is posted.
+static int put_typed(mpigx_win* w, const void* origin, int ocount, int otype, int t, long long target_disp,
+                     long long tdisp, int tcount, int ttype, long long bytes) {
+  mpigx_comm* c = w->c;
+  rt::TypeDesc od, td;
+  if (rt::type_info(otype, &od) || rt::type_info(ttype, &td)) return MPIGX_ERR_TYPE;
+  const bool ttyped = td.derived && !td.contig;
+  RmaType T;
+  int rc;
+  if (ttyped && (rc = rt::type_flatten(ttype, &T))) return rc;
+  long long lo = 0, hi = bytes;
+  if (ttyped && (rc = rt::type_span(ttype, tcount, &lo, &hi))) return rc;
+  if (w->flavor != MPIGX_WIN_FLAVOR_DYNAMIC && (target_disp < 0 || tdisp + lo < 0 || tdisp + hi > w->peer_size[t]))
+    return MPIGX_ERR_RMA_RANGE;
+  reclaim_put_tmps(w, false);
+  const void* src = origin;
+  char* tmp = nullptr;
+  if (od.derived && !od.contig) {
+    if (!(tmp = rt::tmp_alloc(c, bytes))) return MPIGX_ERR_NO_MEM;
+    if ((rc = rt::type_pack(otype, origin, ocount, tmp, bytes, 0, c->device, c->stream))) {
+      rt::tmp_release(c, tmp);
+      return rc;
+    }
+    src = tmp;
+  }
+  rc = sync_stream(c);  // the origin buffer (and its packed copy) is final when the call is made
+  int entry = 0;
+  if (!rc && ttyped) rc = claim_type_entry(w, &entry);
+  uint64_t seq = 0;
+  if (!rc) {
+    if (ttyped) {
+      wshm(w)->ttab[c->rank][entry] = T;
+      rc = post(w, t, RK_PUTT, 0, entry, tdisp, bytes, src, tcount, &seq);
+      if (!rc) w->tt_use[entry] = {true, t, seq};
+    } else {
+      rc = post(w, t, RK_PUT, 0, 0, tdisp, bytes, src, 0, &seq);
+    }
+  }
+  if (tmp) {
+    if (rc) rt::tmp_release(c, tmp);
+    else w->put_tmps.push_back({tmp, t, seq});
+  }
+  return rc;
 }
 
 int mpigx_put(const void* origin_addr, int origin_count, int origin_datatype, int target_rank,
@@ -909,16 +1075,18 @@ int mpigx_put(const void* origin_addr, int origin_count, int origin_datatype, in
   std::lock_guard<rt::BigLock> big(rt::big_lock());  // THREAD_MULTIPLE (runtime.hpp)
   int rc = check_win(w);
   if (rc) return rc;
-  int es;
-  rc = check_xfer(origin_count, origin_datatype, target_count, target_datatype, &es);
+  long long bytes;
+  bool typed;
+  rc = check_xfer(origin_count, origin_datatype, target_count, target_datatype, &bytes, &typed);
   if (rc) return rc;
   rc = check_target(w, target_rank);
   if (rc < 0) return MPIGX_SUCCESS;
   if (rc) return rc;
-  const long long bytes = (long long)origin_count * es;
   if (bytes == 0) return MPIGX_SUCCESS;
   if (!origin_addr) return MPIGX_ERR_BUFFER;
   const long long tdisp = w->flavor == MPIGX_WIN_FLAVOR_DYNAMIC ? target_disp : target_disp * w->peer_du[target_rank];
+  if (typed) return put_typed(w, origin_addr, origin_count, origin_datatype, target_rank, target_disp, tdisp,
+                              target_count, target_datatype, bytes);
   if (w->flavor != MPIGX_WIN_FLAVOR_DYNAMIC && (target_disp < 0 || tdisp + bytes > w->peer_size[target_rank]))
     return MPIGX_ERR_RMA_RANGE;
   rc = sync_stream(w->c);  // the origin buffer is final when the call is made
@@ -931,6 +1099,9 @@ static int acc_common(const void* origin, int ocount, int otype, void* result, i
   int rc = check_win(w);
   if (rc) return rc;
   if (ocount < 0 || tcount < 0 || rcount < 0) return MPIGX_ERR_COUNT;
+  if ((rc = lower_acc_type(&ttype, &tcount)) || (op != MPIGX_NO_OP && (rc = lower_acc_type(&otype, &ocount))) ||
+      (fetch && (rc = lower_acc_type(&rtype, &rcount))))
+    return rc;
   int rep, es, oc;
   rc = rt::acc_check(ttype, op, &rep, &es, &oc);
   if (rc) return rc;

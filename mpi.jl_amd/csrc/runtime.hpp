@@ -107,6 +107,24 @@ struct alignas(64) RmaEnvelope {
 struct RmaBox {
   RmaEnvelope slot[kRmaSlots];
 };
+// Put with a derived TARGET type: datatype handles are process-local, so the
+// origin writes the type's flattened runs into one of its kRmaTypeSlots
+// entries of the window's table (ttab[origin][*]) and the envelope names the
+// entry (RK_PUTT: rep = entry, res_off = target instances).  The origin reuses
+// an entry only after the envelope that named it is done, so the target reads
+// it unsynchronised between `posted` and `done`.  A type of more than
+// kRmaRunCap runs is refused at the origin (MPI_ERR_TYPE).  Fixed cost:
+// kMaxWins x kMaxRanks x kRmaTypeSlots entries of 2072 B = 2.1 MB of the
+// communicator's shm block, and no device memory (the target passes the runs
+// to its kernel as arguments).
+constexpr int kRmaRunCap = 64;  // = kInlineRuns (typed.hpp)
+constexpr int kRmaTypeSlots = 4;
+struct RmaType {
+  long long size, extent;  // packed bytes per instance, bytes between instances
+  int nruns;
+  int pad;
+  TypeRun runs[kRmaRunCap];
+};
 struct DynRegion {
   std::atomic<uint64_t> gen;
   unsigned long long addr, size, buf_id;
@@ -117,6 +135,7 @@ struct WinShm {
   std::atomic<int> lock[kMaxRanks];
   RmaBox box[kMaxRanks][kMaxRanks];  // [origin][target]
   DynRegion dyn[kMaxRanks][kMaxAttach];
+  RmaType ttab[kMaxRanks][kRmaTypeSlots];  // [origin][entry]
 };
 
 struct ShmBlock {
@@ -382,6 +401,22 @@ int type_info(int datatype, TypeDesc* d);  // MPIGX_ERR_TYPE for unknown / uncom
 // `count` elements; enqueued on `s` (device `device`)
 int type_pack(int datatype, const void* typed, long long count, void* contig, long long bytes, int unpack, int device,
               hipStream_t s);
+// The ranges of a v-collective's typed side in one launch (copy.hip
+// seg_pack_kernel): range j = cnt[j] instances from typed + dsp[j] * extent,
+// packed at contig + c_off[j] (unpack = 1: the reverse); nseg <= kMaxRanks.
+int type_pack_seg(int datatype, const void* typed, int nseg, const long long* cnt, const long long* dsp,
+                  const long long* c_off, void* contig, int unpack, int device, hipStream_t s);
+// True bounds [lo, hi) of `count` instances, in bytes from the buffer pointer.
+int type_span(int datatype, long long count, long long* lo, long long* hi);
+// The flattened runs of a committed type (MPIGX_ERR_TYPE past kRmaRunCap runs).
+int type_flatten(int datatype, RmaType* out);
+// `bytes` packed bytes from src through stype to dst through dtype (copy.hip
+// typed_xfer_kernel); flat_xfer: contiguous src, destination type as runs.
+int type_xfer(int stype, const void* src, int dtype, void* dst, long long bytes, int device, hipStream_t s);
+int flat_xfer(const RmaType& d, void* dst, const void* src, long long bytes, hipStream_t s);
+// pooled device temporaries of the communicator (mpigx.cpp tmp_get / tmp_put)
+char* tmp_alloc(mpigx_comm* c, long long bytes);
+void tmp_release(mpigx_comm* c, char* p);
 // rma.cpp
 void rma_progress(mpigx_comm* c);
 void rma_destroy(mpigx_comm* c);

@@ -19,6 +19,15 @@
 // inside the run by division.  HBM gather/scatter; used (a) on the sender to
 // pack into a contiguous temporary, (b) on the receiver fused with the pull
 // over xGMI (contiguous remote source -> typed local destination).
+//
+// Two more kernels use the same map (copy.hip, typed.hpp).  seg_pack_kernel<W>
+// packs or unpacks every block of one side of a v-collective (Gatherv,
+// Scatterv, Allgatherv, Alltoallv) in one launch: up to one segment per rank,
+// blocks dealt to segments by their bytes (type_pack_seg).  typed_xfer_kernel<W>
+// moves a packed stream from a source type map to a destination type map in
+// one pass: one-sided Get with both handles local (type_xfer), and Put at the
+// target, where the target type arrives as flattened runs (type_flatten at
+// the origin, at most kRmaRunCap runs; flat_xfer at the target).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -31,6 +40,7 @@
 #include "handles.hpp"
 #include "launch.hpp"
 #include "runtime.hpp"
+#include "typed.hpp"
 
 using namespace mpigx;
 
@@ -268,6 +278,143 @@ int type_pack(int h, const void* typed, long long count, void* contig, long long
   return launch_pack(s, a) == hipSuccess ? MPIGX_SUCCESS : MPIGX_ERR_INTERN;
 }
 
+int type_pack_seg(int h, const void* typed, int nseg, const long long* cnt, const long long* dsp,
+                  const long long* c_off, void* contig, int unpack, int device, hipStream_t s) {
+  DType* t = lookup(h);
+  if (!t || !t->committed || nseg < 0 || nseg > kMaxRanks) return MPIGX_ERR_TYPE;
+  SegPackArgs a;
+  memset(&a, 0, sizeof a);
+  a.size = t->size;
+  a.extent = t->ub - t->lb;
+  // the unit width divides the type, both bases and every segment's offsets and length
+  unsigned long long g = 0;
+  bool any = false;
+  for (int j = 0; j < nseg; ++j) {
+    a.t_off[j] = dsp[j] * a.extent;
+    a.c_off[j] = c_off[j];
+    const long long bytes = cnt[j] * a.size;
+    if (bytes <= 0) continue;
+    any = true;
+    g |= (unsigned long long)a.t_off[j] | (unsigned long long)a.c_off[j] | (unsigned long long)bytes;
+  }
+  if (!any) return MPIGX_SUCCESS;
+  int rc = device_runs(t, device, &a.runs, &a.pfx);
+  if (rc) return rc;
+  a.nruns = (int)t->runs.size();
+  a.w = unit_of(*t, typed, contig, (long long)(g & 0xf));
+  for (int j = 0; j < nseg; ++j) a.units[j] = cnt[j] > 0 ? cnt[j] * a.size / a.w : 0;
+  a.nseg = nseg;
+  a.unpack = unpack;
+  a.coherent = pull_fences();
+  a.typed = (char*)typed;
+  a.contig = (char*)contig;
+  if (launch_seg_pack(s, a) != hipSuccess) {
+    (void)hipGetLastError();
+    return MPIGX_ERR_INTERN;
+  }
+  return MPIGX_SUCCESS;
+}
+
+int type_span(int h, long long count, long long* lo, long long* hi) {
+  DType f;
+  if (!flat_of(h, &f, true)) return MPIGX_ERR_TYPE;
+  const long long e = f.ub - f.lb, last = count > 0 ? (count - 1) * e : 0;
+  *lo = f.tlb + std::min(0ll, last);
+  *hi = f.tub + std::max(0ll, last);
+  if (count <= 0 || f.size == 0) *lo = *hi = 0;
+  return MPIGX_SUCCESS;
+}
+
+int type_flatten(int h, RmaType* out) {
+  DType f;
+  if (!flat_of(h, &f, true)) return MPIGX_ERR_TYPE;
+  if (f.runs.size() > (size_t)kRmaRunCap) return MPIGX_ERR_TYPE;
+  out->size = f.size;
+  out->extent = f.ub - f.lb;
+  out->nruns = (int)f.runs.size();
+  for (int i = 0; i < out->nruns; ++i) out->runs[i] = f.runs[i];
+  return MPIGX_SUCCESS;
+}
+
+namespace {
+unsigned long long align_bits(const std::vector<TypeRun>& runs, long long size, long long extent) {
+  unsigned long long g = (unsigned long long)extent | (unsigned long long)size;
+  for (const auto& r : runs)
+    g |= (unsigned long long)r.off | (unsigned long long)r.len | (r.n > 1 ? (unsigned long long)r.stride : 0ull);
+  return g;
+}
+int low_bit16(unsigned long long g) {
+  g |= 16ull;
+  return (int)(g & (~g + 1));
+}
+// One side of a typed transfer from a local handle: contiguous types (and
+// predefined ones) are the run-less stream.
+int map_of(int h, int device, TypeMap* m, unsigned long long* bits) {
+  memset(m, 0, sizeof *m);
+  TypeDesc d;
+  int rc = type_info(h, &d);
+  if (rc) return rc;
+  m->size = d.size;
+  m->extent = d.extent;
+  if (d.contig) return MPIGX_SUCCESS;
+  DType* t = lookup(h);
+  rc = device_runs(t, device, &m->runs, &m->pfx);
+  if (rc) return rc;
+  m->nruns = (int)t->runs.size();
+  *bits |= align_bits(t->runs, m->size, m->extent);
+  return MPIGX_SUCCESS;
+}
+}  // namespace
+
+int type_xfer(int stype, const void* src, int dtype, void* dst, long long bytes, int device, hipStream_t s) {
+  if (bytes <= 0) return MPIGX_SUCCESS;
+  TypedXferArgs a;
+  memset(&a, 0, sizeof a);
+  unsigned long long g = (unsigned long long)(uintptr_t)src | (unsigned long long)(uintptr_t)dst |
+                         (unsigned long long)bytes;
+  int rc = map_of(stype, device, &a.s, &g);
+  if (!rc) rc = map_of(dtype, device, &a.d, &g);
+  if (rc) return rc;
+  a.src = (const char*)src;
+  a.dst = (char*)dst;
+  a.w = low_bit16(g);
+  a.coherent = pull_fences();
+  a.units = bytes / a.w;
+  if (launch_typed_xfer(s, a) != hipSuccess) {
+    (void)hipGetLastError();
+    return MPIGX_ERR_INTERN;
+  }
+  return MPIGX_SUCCESS;
+}
+
+int flat_xfer(const RmaType& d, void* dst, const void* src, long long bytes, hipStream_t s) {
+  if (bytes <= 0) return MPIGX_SUCCESS;
+  if (d.nruns < 0 || d.nruns > kRmaRunCap || d.size <= 0) return MPIGX_ERR_TYPE;
+  TypedXferArgs a;
+  memset(&a, 0, sizeof a);
+  std::vector<TypeRun> runs(d.runs, d.runs + d.nruns);
+  for (int i = 0; i < d.nruns; ++i) {
+    a.iruns[i] = d.runs[i];
+    a.ipfx[i + 1] = a.ipfx[i] + d.runs[i].len * d.runs[i].n;
+  }
+  if (a.ipfx[d.nruns] != d.size) return MPIGX_ERR_TYPE;
+  a.d.nruns = d.nruns;
+  a.d.inl = 1;
+  a.d.size = d.size;
+  a.d.extent = d.extent;
+  a.src = (const char*)src;
+  a.dst = (char*)dst;
+  a.w = low_bit16(align_bits(runs, d.size, d.extent) | (unsigned long long)(uintptr_t)src |
+                  (unsigned long long)(uintptr_t)dst | (unsigned long long)bytes);
+  a.coherent = pull_fences();
+  a.units = bytes / a.w;
+  if (launch_typed_xfer(s, a) != hipSuccess) {
+    (void)hipGetLastError();
+    return MPIGX_ERR_INTERN;
+  }
+  return MPIGX_SUCCESS;
+}
+
 }  // namespace rt
 }  // namespace mpigx
 
@@ -501,6 +648,23 @@ static int pack_common(int datatype, void* typed, int count, void* contig, long 
     return MPIGX_ERR_INTERN;
   }
   *position += bytes;
+  return MPIGX_SUCCESS;
+}
+
+int mpigx_pack_segments(const void* typed, int datatype, int nseg, const long long* counts, const long long* displs,
+                        const long long* offsets, void* packed, int unpack, void* stream) {
+  if (nseg < 0 || nseg > kMaxRanks || (nseg && (!counts || !displs || !offsets))) return MPIGX_ERR_ARG;
+  for (int j = 0; j < nseg; ++j)
+    if (counts[j] < 0) return MPIGX_ERR_COUNT;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return MPIGX_ERR_INTERN;
+  const int rc = rt::type_pack_seg(datatype, typed, nseg, counts, displs, offsets, packed, unpack ? 1 : 0, dev,
+                                   (hipStream_t)stream);
+  if (rc) return rc;
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
+    (void)hipGetLastError();
+    return MPIGX_ERR_INTERN;
+  }
   return MPIGX_SUCCESS;
 }
 

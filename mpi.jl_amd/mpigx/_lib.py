@@ -69,6 +69,8 @@ PROTOTYPES = {
     "mpigx_comm_probe": (c_int, [c_void_p, c_int, c_longlong, ctypes.POINTER(ctypes.c_double)]),
     "mpigx_read_probe": (c_int, [ctypes.POINTER(c_void_p), c_int, c_longlong, c_void_p, c_void_p]),
     "mpigx_mix_probe": (c_int, [ctypes.POINTER(c_void_p), c_int, c_longlong, c_void_p, c_void_p]),
+    "mpigx_pack_segments": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_longlong), ctypes.POINTER(c_longlong),
+                                    ctypes.POINTER(c_longlong), c_void_p, c_int, c_void_p]),
     "mpigx_barrier": (c_int, [c_void_p]),
     "mpigx_bcast": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "mpigx_allgather": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),

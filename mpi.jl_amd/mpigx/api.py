@@ -779,6 +779,15 @@ def _side(buf, count, T):
     return _cint(count), T.val
 
 
+def _vtype(buf, T):
+    """Datatype handle of one side of a v-collective: an explicit MPI.Buffer
+    carries its own datatype (a padded struct, a resized vector: one instance
+    per matrix column, a subarray ...), and the counts and displacements of
+    that side are then in units of that type's extent; otherwise the wrapper's
+    element type."""
+    return buf.datatype.val if isinstance(buf, Buffer) else T.val
+
+
 def Allgather_(*args):
     """Allgather!(sendbuf, recvbuf, count, comm) / Allgather!(sendrecvbuf, count, comm)
     — collective.jl:295-311."""
@@ -888,8 +897,8 @@ def Scatterv_(sendbuf, recvbuf, counts, root, comm):
     _assert_minlength(recvbuf, counts[rank])
     T = _eltype(sendbuf) if recvbuf is IN_PLACE else _eltype(recvbuf)
     data = sendbuf if recvbuf is IN_PLACE else recvbuf
-    _call("Scatterv", data, comm, _ptr(sendbuf), _cints(counts), _cints(_disps(counts)), T.val, _ptr(recvbuf),
-          _cint(counts[rank]), T.val, int(root))
+    _call("Scatterv", data, comm, _ptr(sendbuf), _cints(counts), _cints(_disps(counts)), _vtype(sendbuf, T),
+          _ptr(recvbuf), _cint(counts[rank]), _vtype(recvbuf, T), int(root))
     return recvbuf
 
 
@@ -947,8 +956,8 @@ def Gatherv_(sendbuf, recvbuf, counts, root, comm):
     _assert_minlength(sendbuf, counts[rank])
     T = _eltype(recvbuf) if sendbuf is IN_PLACE else _eltype(sendbuf)
     data = recvbuf if sendbuf is IN_PLACE else sendbuf
-    _call("Gatherv", data, comm, _ptr(sendbuf), _cint(counts[rank]), T.val, _ptr(recvbuf), _cints(counts),
-          _cints(_disps(counts)), T.val, int(root))
+    _call("Gatherv", data, comm, _ptr(sendbuf), _cint(counts[rank]), _vtype(sendbuf, T), _ptr(recvbuf),
+          _cints(counts), _cints(_disps(counts)), _vtype(recvbuf, T), int(root))
     return recvbuf if isroot else None
 
 
@@ -970,8 +979,8 @@ def Allgatherv_(*args):
     _assert_minlength(recvbuf, sum(counts))
     _assert_minlength(sendbuf, sendcnt)
     T = _eltype(recvbuf)
-    _call("Allgatherv", recvbuf, comm, _ptr(sendbuf), _cint(sendcnt), T.val, _ptr(recvbuf), _cints(counts),
-          _cints(_disps(counts)), T.val)
+    _call("Allgatherv", recvbuf, comm, _ptr(sendbuf), _cint(sendcnt), _vtype(sendbuf, T), _ptr(recvbuf),
+          _cints(counts), _cints(_disps(counts)), _vtype(recvbuf, T))
     return recvbuf
 
 
@@ -984,10 +993,11 @@ def Alltoallv_(sendbuf, recvbuf, scounts, rcounts, comm):
     """Alltoallv!(sendbuf, recvbuf, scounts, rcounts, comm) — collective.jl:545-559."""
     _assert_minlength(sendbuf, sum(scounts))
     _assert_minlength(recvbuf, sum(rcounts))
-    assert _eltype(sendbuf) == _eltype(recvbuf)
-    T = _eltype(sendbuf)
-    _call("Alltoallv", recvbuf, comm, _ptr(sendbuf), _cints(scounts), _cints(_disps(scounts)), T.val,
-          _ptr(recvbuf), _cints(rcounts), _cints(_disps(rcounts)), T.val)
+    if not isinstance(sendbuf, Buffer) and not isinstance(recvbuf, Buffer):
+        assert _eltype(sendbuf) == _eltype(recvbuf)
+    T = _eltype(recvbuf)
+    _call("Alltoallv", recvbuf, comm, _ptr(sendbuf), _cints(scounts), _cints(_disps(scounts)), _vtype(sendbuf, T),
+          _ptr(recvbuf), _cints(rcounts), _cints(_disps(rcounts)), _vtype(recvbuf, T))
     return recvbuf
 
 

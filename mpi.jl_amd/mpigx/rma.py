@@ -339,43 +339,62 @@ def _count_of(x):
     return b.size if isinstance(b, np.ndarray) else b.numel()
 
 
-def Get(origin_buffer, *args):
-    """Get(origin, count, target_rank, target_disp, win) (onesided.jl:150-159)
-    or Get(origin, target_rank, win) (:160-166: count = length, disp 0)."""
+def _operand(x, count=None):
+    """(count, engine handle, host libmpi handle) of one side of Get / Put: an
+    MPI.Buffer carries its own count and datatype (a padded struct built by
+    Datatype(dtype), a vector, a subarray ...); an array goes by its length
+    (or `count`) and element type."""
+    from .api import Buffer, Datatype
+    if isinstance(x, Buffer):
+        return int(x.count), x.datatype.val, x.datatype.host
+    dt = Datatype(_unwrap(x).dtype)
+    return int(_count_of(x) if count is None else count), dt.val, dt.host
+
+
+def _xfer_args(origin_buffer, args, target):
+    """Arguments of Get / Put.  `target`: the target side's (count, datatype)
+    as an MPI.Buffer without data or a (count, Datatype) pair when it differs
+    from the origin's (a C-ABI capability; MPI.jl's wrappers pass the
+    origin's count and datatype for both)."""
+    from .api import Buffer
     if len(args) == 2:
-        count, (target_rank, win), target_disp = _count_of(origin_buffer), args, 0
+        count, (target_rank, win), target_disp = None, args, 0
     else:
         count, target_rank, target_disp, win = args
-    dt = _dtype_val(origin_buffer)
+    oc, odt, ohost = _operand(origin_buffer, count)
+    tc, tdt, thost = oc, odt, ohost
+    if target is not None:
+        tc, tdt, thost = _operand(target if isinstance(target, Buffer) else Buffer(None, target[0], target[1]))
+    return (oc, odt, ohost), (tc, tdt, thost), int(target_rank), int(target_disp), win
+
+
+def Get(origin_buffer, *args, target=None):
+    """Get(origin, count, target_rank, target_disp, win) (onesided.jl:150-159)
+    or Get(origin, target_rank, win) (:160-166: count = length, disp 0).
+    `origin` may be an MPI.Buffer (count + datatype); `target`: see _xfer_args."""
+    (oc, odt, ohost), (tc, tdt, thost), target_rank, target_disp, win = _xfer_args(origin_buffer, args, target)
     if _host(win):
         o = _unwrap(origin_buffer)
-        _hcheck(hostmpi.lib().MPI_Get(_hptr(o), int(count), dt, int(target_rank), _aint(target_disp), int(count), dt,
-                                      win.val))
+        _hcheck(hostmpi.lib().MPI_Get(_hptr(o), oc, ohost, target_rank, _aint(target_disp), tc, thost, win.val))
         return
     b = _unwrap(origin_buffer)
     dst = _to_dev(win, b)
-    _dev_call(win, "mpigx_get", _dptr(dst), int(count), dt, int(target_rank), ctypes.c_longlong(int(target_disp)),
-              int(count), dt, win.val)
+    _dev_call(win, "mpigx_get", _dptr(dst), oc, odt, target_rank, ctypes.c_longlong(target_disp), tc, tdt, win.val)
     if isinstance(b, np.ndarray):
         win._deferred.append((dst, b))
 
 
-def Put(origin_buffer, *args):
+def Put(origin_buffer, *args, target=None):
     """Put(origin, count, target_rank, target_disp, win) (onesided.jl:168-177)
-    or Put(origin, target_rank, win) (:178-184)."""
-    if len(args) == 2:
-        count, (target_rank, win), target_disp = _count_of(origin_buffer), args, 0
-    else:
-        count, target_rank, target_disp, win = args
-    dt = _dtype_val(origin_buffer)
+    or Put(origin, target_rank, win) (:178-184).  `origin` may be an
+    MPI.Buffer (count + datatype); `target`: see _xfer_args."""
+    (oc, odt, ohost), (tc, tdt, thost), target_rank, target_disp, win = _xfer_args(origin_buffer, args, target)
     if _host(win):
         o = _unwrap(origin_buffer)
-        _hcheck(hostmpi.lib().MPI_Put(_hptr(o), int(count), dt, int(target_rank), _aint(target_disp), int(count), dt,
-                                      win.val))
+        _hcheck(hostmpi.lib().MPI_Put(_hptr(o), oc, ohost, target_rank, _aint(target_disp), tc, thost, win.val))
         return
     src = _to_dev(win, origin_buffer)
-    _dev_call(win, "mpigx_put", _dptr(src), int(count), dt, int(target_rank), ctypes.c_longlong(int(target_disp)),
-              int(count), dt, win.val)
+    _dev_call(win, "mpigx_put", _dptr(src), oc, odt, target_rank, ctypes.c_longlong(target_disp), tc, tdt, win.val)
 
 
 def _opval(op, x):

@@ -467,10 +467,24 @@ int mpigx_get(void *origin_addr, int origin_count, int origin_datatype, int targ
               long long target_disp, int target_count, int target_datatype, mpigx_win_t win);
 int mpigx_put(const void *origin_addr, int origin_count, int origin_datatype, int target_rank,
               long long target_disp, int target_count, int target_datatype, mpigx_win_t win);
-/* MPI_Fetch_and_op / MPI_Accumulate / MPI_Get_accumulate take predefined
- * types and derived types that are a contiguous run of ONE predefined type
- * (reduced element-wise, as in the reductions); any other derived type is
- * MPI_ERR_TYPE there — a deliberate limit.
+/* MPI_Accumulate / MPI_Get_accumulate take, for origin, target and result
+ * independently, any committed datatype whose bytes all belong to ONE
+ * predefined type: predefined types, contiguous derived types, and
+ * non-contiguous ones (vectors, hvectors, subarrays, resized types whose
+ * instances interleave, structs of one type with holes).  The op is applied
+ * element by element through the type maps, as MPICH does; accumulates to one
+ * target stay ordered per origin and atomic per element.  The sides must agree
+ * in their predefined type and in their number of elements, and every run
+ * offset, run length, stride and extent of a non-contiguous type must be a
+ * whole number of elements, else MPI_ERR_TYPE.  Limits that remain
+ * (MPI_ERR_TYPE, before anything is posted, the window untouched): a type of
+ * mixed predefined types on any side, MPI_REPLACE / MPI_NO_OP included, and a
+ * non-contiguous TARGET type that flattens to more than 64 runs (as for
+ * MPI_Put; origin and result types have no cap).  The target type's true span
+ * over target_count instances must lie in the window (MPI_ERR_RMA_RANGE).
+ * MPI_Fetch_and_op takes predefined types and derived types that are a
+ * contiguous run of one predefined type; any other derived type is
+ * MPI_ERR_TYPE there.
  * MPI_Fetch_and_op — onesided.jl:186-195 */
 int mpigx_fetch_and_op(const void *origin_addr, void *result_addr, int datatype, int target_rank,
                        long long target_disp, int op, mpigx_win_t win);

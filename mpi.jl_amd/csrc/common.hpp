@@ -346,6 +346,31 @@ struct AccArgs {
 struct TypeRun {
   long long off, len, n, stride;
 };
+
+// RMA accumulate through a non-contiguous TARGET type (kernels.hpp
+// acc_typed_kernel), in an argument block of its own: AccArgs and the
+// contiguous launch stay as they are.  Element i of the launch is element
+// first + i of the packed stream of the target type's instances; it is read
+// and written in the window at dst + typed_off((first + i) * sizeof(T)),
+// while src[i] / res[i] are packed.  The type's flattened runs and their
+// per-instance packed-byte prefix travel inline (the target has no handle of
+// the origin's type).  Launch geometry: one thread per kAccTypedU elements,
+// at most kAccTypedGridCap blocks (the kernel strides over the rest).
+constexpr int kAccTypedRuns = 64;
+constexpr int kAccTypedU = 4;
+constexpr int kAccTypedGridCap = 1024;
+struct AccTypedArgs {
+  const void* src;
+  void* dst;
+  void* res;  // may be null
+  long long count;
+  long long first;
+  long long size, extent;  // packed bytes per instance, bytes between instances
+  int nruns;
+  int coherent;  // as AccArgs
+  TypeRun runs[kAccTypedRuns];
+  long long pfx[kAccTypedRuns + 1];
+};
 // Pack (typed -> contiguous) or unpack (contiguous -> typed) `units` W-byte
 // units of a packed stream of instances of one type (extent apart).
 struct PackArgs {

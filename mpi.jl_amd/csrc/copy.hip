@@ -5,6 +5,7 @@
 #include "kernels.hpp"
 #include "launch.hpp"
 #include "typed.hpp"
+#include "typed_off.hpp"
 
 namespace mpigx {
 
@@ -507,26 +508,8 @@ hipError_t launch_pack(hipStream_t s, const PackArgs& a) {
   return hipGetLastError();
 }
 
-// Packed byte p of a stream of instances of one type -> byte offset from the
-// typed buffer's pointer (pack_kernel's map: instance, run by binary search
-// over the per-instance prefix, block, byte).  nruns = 0: contiguous.
-__device__ __forceinline__ long long typed_off(const TypeRun* runs, const long long* pfx, int nruns, long long size,
-                                               long long extent, long long p) {
-  if (nruns == 0) return p;
-  const long long k = p / size, r = p - k * size;
-  int lo = 0;
-  if (nruns > 1) {
-    int hi = nruns - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (pfx[mid] <= r) lo = mid;
-      else hi = mid - 1;
-    }
-  }
-  const TypeRun R = runs[lo];
-  const long long q = r - pfx[lo], i = q / R.len, b = q - i * R.len;
-  return k * extent + R.off + i * R.stride + b;
-}
+// (typed_off, the packed-byte -> typed-offset map of the kernels below, lives
+// in typed_off.hpp: the typed accumulate of kernels.hpp uses it too)
 
 template <int W>
 struct UnitOf {

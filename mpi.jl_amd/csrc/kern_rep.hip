@@ -53,6 +53,7 @@
 #define MPIGX_RING_FN(K) MPIGX_CAT4(launch_ring_, MPIGX_OP_NAME(K), _o, K)
 #define MPIGX_SCAN_FN(K) MPIGX_CAT4(launch_scan_, MPIGX_OP_NAME(K), _o, K)
 #define MPIGX_ACC_FN(K) MPIGX_CAT4(launch_acc_, MPIGX_OP_NAME(K), _o, K)
+#define MPIGX_ACCT_FN(K) MPIGX_CAT4(launch_acc_typed_, MPIGX_OP_NAME(K), _o, K)
 
 namespace mpigx {
 namespace {
@@ -207,7 +208,8 @@ int occ_op(int kind, int a, int b) {
   hipError_t MPIGX_FOLD_FN(K)(int nmax, int sched, dim3 grid, hipStream_t s, const FoldArgs& a);      \
   hipError_t MPIGX_RING_FN(K)(dim3 grid, hipStream_t s, const RingArgs& a);                            \
   hipError_t MPIGX_SCAN_FN(K)(dim3 grid, hipStream_t s, const ScanArgs& a);                            \
-  hipError_t MPIGX_ACC_FN(K)(dim3 grid, hipStream_t s, const AccArgs& a);
+  hipError_t MPIGX_ACC_FN(K)(dim3 grid, hipStream_t s, const AccArgs& a);                              \
+  hipError_t MPIGX_ACCT_FN(K)(dim3 grid, hipStream_t s, const AccTypedArgs& a);
 MPIGX_DECL_OP(0) MPIGX_DECL_OP(1) MPIGX_DECL_OP(2) MPIGX_DECL_OP(3) MPIGX_DECL_OP(4) MPIGX_DECL_OP(5)
 MPIGX_DECL_OP(6) MPIGX_DECL_OP(7) MPIGX_DECL_OP(8) MPIGX_DECL_OP(9) MPIGX_DECL_OP(16) MPIGX_DECL_OP(17)
 #undef MPIGX_DECL_OP
@@ -246,6 +248,13 @@ MPIGX_DECL_OP(6) MPIGX_DECL_OP(7) MPIGX_DECL_OP(8) MPIGX_DECL_OP(9) MPIGX_DECL_O
       return hipGetLastError();                                                                        \
     }                                                                                                  \
     return hipErrorInvalidValue;                                                                       \
+  }                                                                                                    \
+  hipError_t MPIGX_ACCT_FN(K)(dim3 grid, hipStream_t s, const AccTypedArgs& a) {                       \
+    if constexpr (valid_op(K)) {                                                                       \
+      hipLaunchKernelGGL((acc_typed_kernel<OpOf<K>::type, T>), grid, dim3(kThreads), 0, s, a);         \
+      return hipGetLastError();                                                                        \
+    }                                                                                                  \
+    return hipErrorInvalidValue;                                                                       \
   }
 
 #if MPIGX_PART == 0
@@ -268,6 +277,14 @@ hipError_t MPIGX_ACC_FN(16)(dim3 grid, hipStream_t s, const AccArgs& a) {
 }
 hipError_t MPIGX_ACC_FN(17)(dim3 grid, hipStream_t s, const AccArgs& a) {
   hipLaunchKernelGGL((acc_kernel<OpNoop, T>), grid, dim3(kThreads), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t MPIGX_ACCT_FN(16)(dim3 grid, hipStream_t s, const AccTypedArgs& a) {
+  hipLaunchKernelGGL((acc_typed_kernel<OpReplace, T>), grid, dim3(kThreads), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t MPIGX_ACCT_FN(17)(dim3 grid, hipStream_t s, const AccTypedArgs& a) {
+  hipLaunchKernelGGL((acc_typed_kernel<OpNoop, T>), grid, dim3(kThreads), 0, s, a);
   return hipGetLastError();
 }
 
@@ -334,6 +351,12 @@ hipError_t MPIGX_CAT(launch_acc_, MPIGX_REP_NAME)(int op, dim3 grid, hipStream_t
   if (op == O_REPLACE) return MPIGX_ACC_FN(16)(grid, s, a);
   if (op == O_NOOP) return MPIGX_ACC_FN(17)(grid, s, a);
   MPIGX_SWITCH(MPIGX_ACC_FN, grid, s, a)
+}
+// ... through a non-contiguous target type (acc_typed_kernel), same op set
+hipError_t MPIGX_CAT(launch_acc_typed_, MPIGX_REP_NAME)(int op, dim3 grid, hipStream_t s, const AccTypedArgs& a) {
+  if (op == O_REPLACE) return MPIGX_ACCT_FN(16)(grid, s, a);
+  if (op == O_NOOP) return MPIGX_ACCT_FN(17)(grid, s, a);
+  MPIGX_SWITCH(MPIGX_ACCT_FN, grid, s, a)
 }
 #undef MPIGX_SWITCH
 #else

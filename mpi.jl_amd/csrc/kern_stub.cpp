@@ -28,4 +28,7 @@ hipError_t MPIGX_CAT(launch_ring_, MPIGX_REP_NAME)(int, dim3, hipStream_t, const
 hipError_t MPIGX_CAT(launch_acc_, MPIGX_REP_NAME)(int, dim3, hipStream_t, const AccArgs&) {
   return hipErrorInvalidValue;
 }
+hipError_t MPIGX_CAT(launch_acc_typed_, MPIGX_REP_NAME)(int, dim3, hipStream_t, const AccTypedArgs&) {
+  return hipErrorInvalidValue;
+}
 }  // namespace mpigx

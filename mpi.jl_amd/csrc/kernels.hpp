@@ -16,6 +16,7 @@
 //   barrier(b) ... final barrier(b): peers finished reading my staging.
 #pragma once
 #include "device.hpp"
+#include "typed_off.hpp"
 
 namespace mpigx {
 
@@ -1122,6 +1123,95 @@ __global__ __launch_bounds__(kThreads) void acc_kernel(AccArgs A) {
     if (res) res[i] = t;
     if constexpr (OP::code == O_REPLACE) dst[i] = src[i];
     else if constexpr (OP::code != O_NOOP) dst[i] = OP::apply(t, src[i]);
+  }
+  pull_release(A.coherent);
+}
+
+// ---------------------------------------------------------------------------
+// acc_typed_kernel<OP,T>: the same accumulate through a non-contiguous target
+// datatype (common.hpp AccTypedArgs).  Element i of the launch lives in the
+// window at dst + typed_off((first + i) * sizeof(T)) (typed_off.hpp: the map
+// of the byte movers); the origin's elements (src, packed by the origin) and
+// the old values (res) are contiguous.  Ops, operand roles and the pull
+// bracket are acc_kernel's.  A gather / scatter on the window side: U
+// elements per thread have their addresses resolved first, then all their
+// loads are issued before any store.  The run list is searched with per-lane
+// indices, so it is staged in LDS (as typed_xfer_kernel does: kernel
+// arguments indexed at run time would go to scratch).
+// ---------------------------------------------------------------------------
+// An element held as raw bits: arrays of the two-member complex structs were
+// not kept in registers by the compiler (acc_typed_kernel<OpReplace, c128> came
+// out with an LDS copy of one array and a private segment for the other).
+template <int N> struct AccRaw;
+template <> struct AccRaw<1> { using type = uint8_t; };
+template <> struct AccRaw<2> { using type = uint16_t; };
+template <> struct AccRaw<4> { using type = uint32_t; };
+template <> struct AccRaw<8> { using type = uint64_t; };
+template <> struct AccRaw<16> { typedef double type __attribute__((ext_vector_type(2))); };
+template <class T>
+__device__ __forceinline__ typename AccRaw<sizeof(T)>::type acc_ld(const T* p) {
+  typename AccRaw<sizeof(T)>::type r;
+  __builtin_memcpy(&r, p, sizeof(T));
+  return r;
+}
+template <class T>
+__device__ __forceinline__ void acc_st(T* p, typename AccRaw<sizeof(T)>::type r) {
+  __builtin_memcpy(p, &r, sizeof(T));
+}
+template <class OP, class T>
+__device__ __forceinline__ typename AccRaw<sizeof(T)>::type acc_apply(typename AccRaw<sizeof(T)>::type t,
+                                                                      typename AccRaw<sizeof(T)>::type s) {
+  T a, b;
+  __builtin_memcpy(&a, &t, sizeof(T));
+  __builtin_memcpy(&b, &s, sizeof(T));
+  const T c = OP::apply(a, b);
+  typename AccRaw<sizeof(T)>::type r;
+  __builtin_memcpy(&r, &c, sizeof(T));
+  return r;
+}
+
+template <class OP, class T>
+__global__ __launch_bounds__(kThreads) void acc_typed_kernel(AccTypedArgs A) {
+  using R = typename AccRaw<sizeof(T)>::type;
+  __shared__ TypeRun sruns[kAccTypedRuns];
+  __shared__ long long spfx[kAccTypedRuns + 1];
+  for (int i = threadIdx.x; i < kAccTypedRuns; i += blockDim.x) sruns[i] = A.runs[i];
+  for (int i = threadIdx.x; i <= kAccTypedRuns; i += blockDim.x) spfx[i] = A.pfx[i];
+  __syncthreads();
+  const T* __restrict__ src = reinterpret_cast<const T*>(A.src);
+  char* dst = reinterpret_cast<char*>(A.dst);
+  T* __restrict__ res = reinterpret_cast<T*>(A.res);
+  pull_acquire(A.coherent);
+  const long long n = A.count, nt = (long long)gridDim.x * blockDim.x, first = A.first;
+  const long long size = A.size, extent = A.extent;
+  const int nruns = A.nruns;
+  constexpr long long ES = (long long)sizeof(T);
+  constexpr int U = kAccTypedU;  // independent elements in flight per thread
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + (U - 1) * nt < n; i += U * nt) {
+    T* p[U];
+    R t[U], s[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      p[u] = reinterpret_cast<T*>(dst + typed_off(sruns, spfx, nruns, size, extent, (first + i + u * nt) * ES));
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      t[u] = acc_ld(p[u]);
+      if constexpr (OP::code != O_NOOP) s[u] = acc_ld(src + i + u * nt);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (res) acc_st(res + i + u * nt, t[u]);
+      if constexpr (OP::code == O_REPLACE) acc_st(p[u], s[u]);
+      else if constexpr (OP::code != O_NOOP) acc_st(p[u], acc_apply<OP, T>(t[u], s[u]));
+    }
+  }
+  for (; i < n; i += nt) {
+    T* p = reinterpret_cast<T*>(dst + typed_off(sruns, spfx, nruns, size, extent, (first + i) * ES));
+    const R t = acc_ld(p);
+    if (res) acc_st(res + i, t);
+    if constexpr (OP::code == O_REPLACE) acc_st(p, acc_ld(src + i));
+    else if constexpr (OP::code != O_NOOP) acc_st(p, acc_apply<OP, T>(t, acc_ld(src + i)));
   }
   pull_release(A.coherent);
 }

@@ -10,6 +10,7 @@ namespace mpigx {
 
 using FoldLauncher = hipError_t (*)(int op, int nmax, int sched, dim3 grid, hipStream_t s, const FoldArgs& a);
 using AccLauncher = hipError_t (*)(int op, dim3 grid, hipStream_t s, const AccArgs& a);
+using AccTypedLauncher = hipError_t (*)(int op, dim3 grid, hipStream_t s, const AccTypedArgs& a);
 using ScanLauncher = hipError_t (*)(int op, dim3 grid, hipStream_t s, const ScanArgs& a);
 using RingLauncher = hipError_t (*)(int op, dim3 grid, hipStream_t s, const RingArgs& a);
 
@@ -36,7 +37,8 @@ inline bool arzc_shape(int n, int ntree, int rem, int* nmax, int* shape) {
   hipError_t launch_fold_##NAME(int op, int nmax, int sched, dim3 grid, hipStream_t s, const FoldArgs& a); \
   hipError_t launch_scan_##NAME(int op, dim3 grid, hipStream_t s, const ScanArgs& a); \
   hipError_t launch_ring_##NAME(int op, dim3 grid, hipStream_t s, const RingArgs& a); \
-  hipError_t launch_acc_##NAME(int op, dim3 grid, hipStream_t s, const AccArgs& a);
+  hipError_t launch_acc_##NAME(int op, dim3 grid, hipStream_t s, const AccArgs& a); \
+  hipError_t launch_acc_typed_##NAME(int op, dim3 grid, hipStream_t s, const AccTypedArgs& a);
 MPIGX_DECL_REP(i8) MPIGX_DECL_REP(u8) MPIGX_DECL_REP(i16) MPIGX_DECL_REP(u16)
 MPIGX_DECL_REP(i32) MPIGX_DECL_REP(u32) MPIGX_DECL_REP(i64) MPIGX_DECL_REP(u64)
 MPIGX_DECL_REP(f32) MPIGX_DECL_REP(f64) MPIGX_DECL_REP(c64) MPIGX_DECL_REP(c128)

@@ -16,7 +16,10 @@
 //                  Accumulate), writes old values of Get_accumulate /
 //                  Fetch_and_op into its scratch slot for that origin, drains
 //                  the stream and stores done = seq + 1.  The origin then
-//                  pulls the old values from that slot.
+//                  pulls the old values from that slot.  Through a
+//                  non-contiguous target type (acc_typed below) the envelope
+//                  names the type's runs in the window's type table and the
+//                  target applies acc_typed_kernel<OP,T> through them.
 // One stream applies every envelope a target receives, so accumulates are
 // atomic per element and ordered per origin (MPI-3 §11.7.1 defaults).
 // Progress runs inside every mpigx call that waits (collectives' host spin,
@@ -47,7 +50,18 @@ namespace {
 
 // RK_PUTT: Put through a derived target type (runtime.hpp RmaType): count =
 // packed bytes, rep = the origin's table entry, res_off = target instances
-enum RmaKind { RK_PUT = 1, RK_ACC = 2, RK_GACC = 3, RK_PUTT = 4 };
+// RK_ACCT / RK_GACCT: Accumulate / Get_accumulate through a non-contiguous
+// target type: count = elements of this envelope, rep = their representation,
+// tent = the origin's table entry, tcount = target instances, first = the
+// envelope's first element in the packed stream of those instances
+enum RmaKind { RK_PUT = 1, RK_ACC = 2, RK_GACC = 3, RK_PUTT = 4, RK_ACCT = 5, RK_GACCT = 6 };
+static_assert(kAccTypedRuns == kRmaRunCap, "a table entry's runs fit acc_typed_kernel's arguments");
+
+// the typed fields of an envelope (runtime.hpp RmaEnvelope)
+struct TypedRef {
+  int entry;
+  long long tcount, first;
+};
 
 AccLauncher acc_launcher(int rep) {
   switch (rep) {
@@ -64,6 +78,25 @@ AccLauncher acc_launcher(int rep) {
     case R_C64: return launch_acc_c64;
     case R_C128: return launch_acc_c128;
     case R_BF16: return launch_acc_bf16;
+    default: return nullptr;
+  }
+}
+
+AccTypedLauncher acc_typed_launcher(int rep) {
+  switch (rep) {
+    case R_I8: return launch_acc_typed_i8;
+    case R_U8: return launch_acc_typed_u8;
+    case R_I16: return launch_acc_typed_i16;
+    case R_U16: return launch_acc_typed_u16;
+    case R_I32: return launch_acc_typed_i32;
+    case R_U32: return launch_acc_typed_u32;
+    case R_I64: return launch_acc_typed_i64;
+    case R_U64: return launch_acc_typed_u64;
+    case R_F32: return launch_acc_typed_f32;
+    case R_F64: return launch_acc_typed_f64;
+    case R_C64: return launch_acc_typed_c64;
+    case R_C128: return launch_acc_typed_c128;
+    case R_BF16: return launch_acc_typed_bf16;
     default: return nullptr;
   }
 }
@@ -239,6 +272,26 @@ int apply_one(mpigx_win* w, int o, RmaEnvelope* e, hipStream_t ws) {
     long long lo, hi;
     flat_span(*T, e->res_off, &lo, &hi);
     dst = local_target(w, e->tdisp, hi - lo, lo);
+  } else if (e->kind == RK_ACCT || e->kind == RK_GACCT) {
+    // the entry as for RK_PUTT, and what the kernel relies on: whole elements
+    // per run and instance, this envelope's elements inside the stream of
+    // tcount instances, and those instances' true span inside my window
+    if (e->tent < 0 || e->tent >= kRmaTypeSlots) return MPIGX_ERR_INTERN;
+    T = &wshm(w)->ttab[o][e->tent];
+    if (T->nruns < 1 || T->nruns > kRmaRunCap || T->size <= 0 || T->extent % esize) return MPIGX_ERR_TYPE;
+    long long packed = 0;
+    for (int i = 0; i < T->nruns; ++i) {
+      const TypeRun& r = T->runs[i];
+      if (r.len <= 0 || r.n < 1 || r.off % esize || r.len % esize || (r.n > 1 && r.stride % esize))
+        return MPIGX_ERR_TYPE;
+      packed += r.len * r.n;
+    }
+    if (packed != T->size || e->tcount < 1 || e->first < 0 || e->count < 1 ||
+        (e->first + e->count) * esize > e->tcount * T->size)
+      return MPIGX_ERR_TYPE;
+    long long lo, hi;
+    flat_span(*T, e->tcount, &lo, &hi);
+    dst = local_target(w, e->tdisp, hi - lo, lo);
   } else {
     dst = local_target(w, e->tdisp, bytes);
   }
@@ -265,6 +318,31 @@ int apply_one(mpigx_win* w, int o, RmaEnvelope* e, hipStream_t ws) {
     a.src[0] = src;
     a.bytes[0] = bytes;
     return launch_xfer(ws, a) == hipSuccess ? MPIGX_SUCCESS : MPIGX_ERR_INTERN;
+  }
+  if (e->kind == RK_ACCT || e->kind == RK_GACCT) {
+    AccTypedArgs a;
+    memset(&a, 0, sizeof a);
+    a.src = src;
+    a.dst = dst;
+    a.count = e->count;
+    a.first = e->first;
+    a.size = T->size;
+    a.extent = T->extent;
+    a.nruns = T->nruns;
+    a.coherent = rt::pull_fences();
+    for (int i = 0; i < T->nruns; ++i) {
+      a.runs[i] = T->runs[i];
+      a.pfx[i + 1] = a.pfx[i] + T->runs[i].len * T->runs[i].n;
+    }
+    if (e->kind == RK_GACCT) {
+      if (e->res_off < 0 || e->res_off + bytes > w->slot_bytes * c->n) return MPIGX_ERR_INTERN;
+      a.res = w->scratch + e->res_off;
+    }
+    AccTypedLauncher L = acc_typed_launcher(rep);
+    if (!L) return MPIGX_ERR_TYPE;
+    long long g = (e->count + kAccTypedU * kThreads - 1) / (kAccTypedU * kThreads);
+    g = std::max(1ll, std::min(g, (long long)kAccTypedGridCap));
+    return L(e->op, dim3((unsigned)g), ws, a) == hipSuccess ? MPIGX_SUCCESS : MPIGX_ERR_INTERN;
   }
   AccArgs a;
   a.src = src;
@@ -328,7 +406,7 @@ int spin_progress(mpigx_win* w, Deadline& d) {
 }
 
 int post(mpigx_win* w, int t, int kind, int op, int rep, long long tdisp, long long count, const void* origin,
-         long long res_off, uint64_t* seq_out) {
+         long long res_off, uint64_t* seq_out, const TypedRef* tr = nullptr) {
   mpigx_comm* c = w->c;
   RmaEnvelope tmp;
   memset((void*)&tmp, 0, sizeof tmp);
@@ -364,6 +442,9 @@ int post(mpigx_win* w, int t, int kind, int op, int rep, long long tdisp, long l
   e->tdisp = tdisp;
   e->count = count;
   e->res_off = res_off;
+  e->tent = tr ? tr->entry : 0;
+  e->tcount = tr ? tr->tcount : 0;
+  e->first = tr ? tr->first : 0;
   e->buf_id = tmp.buf_id;
   e->off = tmp.off;
   e->raw = tmp.raw;
@@ -512,10 +593,13 @@ int check_xfer(int ocount, int otype, int tcount, int ttype, long long* bytes, b
   return MPIGX_SUCCESS;
 }
 
-// Accumulate / Get_accumulate / Fetch_and_op take a derived type only if it is
-// a contiguous run of ONE predefined type, lowered to that type (as the
-// reductions do, mpigx.cpp lower_reduce_type); any other derived type is
-// MPI_ERR_TYPE.
+// The contiguous path of Accumulate / Get_accumulate / Fetch_and_op: a
+// predefined type, or a derived type that is a contiguous run of ONE
+// predefined type, lowered to that type (as the reductions do, mpigx.cpp
+// lower_reduce_type) -> acc_kernel.  Accumulate and Get_accumulate calls with
+// a non-contiguous type on any side never get here (acc_common sends them to
+// acc_typed); for Fetch_and_op, and for contiguous types of mixed basic type,
+// any other derived type is MPI_ERR_TYPE.
 int lower_acc_type(int* datatype, int* count) {
   if (rt::dtype_size(*datatype) >= 0) return MPIGX_SUCCESS;
   rt::TypeDesc d;
@@ -1094,11 +1178,137 @@ int mpigx_put(const void* origin_addr, int origin_count, int origin_datatype, in
   return post(w, target_rank, RK_PUT, 0, 0, tdisp, bytes, origin_addr, 0, nullptr);
 }
 
+// One side (origin, target or result) of an accumulate through derived types:
+// every byte belongs to ONE predefined type (TypeDesc::basic), `elems`
+// elements of it in `count` instances; `typed`: not contiguous, so the side
+// goes through its type map, whose offsets must then be whole elements.
+struct AccSide {
+  rt::TypeDesc d;
+  long long elems = 0;
+  bool typed = false;
+};
+static int acc_side(int type, int count, AccSide* s) {
+  if (rt::type_info(type, &s->d)) return MPIGX_ERR_TYPE;
+  const int bs = s->d.basic ? rt::dtype_size(s->d.basic) : -1;
+  if (bs <= 0 || s->d.size % bs) return MPIGX_ERR_TYPE;
+  s->elems = s->d.size * count / bs;
+  s->typed = s->d.derived && !s->d.contig;
+  if (s->typed && rt::type_elem_aligned(type, bs)) return MPIGX_ERR_TYPE;
+  return MPIGX_SUCCESS;
+}
+static bool noncontig(int type) {
+  rt::TypeDesc d;
+  return rt::type_info(type, &d) == MPIGX_SUCCESS && d.derived && !d.contig;
+}
+
+// Accumulate / Get_accumulate with a non-contiguous derived type on any side.
+// Origin: packed into a pooled temporary that lives until its envelope is done
+// (put_typed's scheme).  Target: its flattened runs travel in my row of the
+// window's type table and the target applies the op through them
+// (acc_typed_kernel); a contiguous target takes today's RK_ACC / RK_GACC.
+// Result: the chunks are pulled into a pooled temporary and unpacked through
+// the result type at the end.  Every refusal happens before anything is posted.
+static int acc_typed(const void* origin, int ocount, int otype, void* result, int rcount, int rtype, int t,
+                     long long tdisp_el, int tcount, int ttype, int op, mpigx_win* w, bool fetch) {
+  mpigx_comm* c = w->c;
+  AccSide T, O, R;
+  int rc = acc_side(ttype, tcount, &T);
+  if (rc) return rc;
+  int rep, es, oc;
+  if ((rc = rt::acc_check(T.d.basic, op, &rep, &es, &oc))) return rc;
+  if (oc != O_NOOP) {
+    if ((rc = acc_side(otype, ocount, &O))) return rc;
+    if (O.d.basic != T.d.basic || O.elems != T.elems) return MPIGX_ERR_TYPE;
+  }
+  if (fetch) {
+    if ((rc = acc_side(rtype, rcount, &R))) return rc;
+    if (R.d.basic != T.d.basic || R.elems != T.elems) return MPIGX_ERR_TYPE;
+  }
+  RmaType F;
+  if (T.typed && (rc = rt::type_flatten(ttype, &F))) return rc;  // more than kRmaRunCap runs
+  rc = check_target(w, t);
+  if (rc < 0) return MPIGX_SUCCESS;
+  if (rc) return rc;
+  const long long count = T.elems, bytes = count * es;
+  if (count == 0) return MPIGX_SUCCESS;
+  if ((oc != O_NOOP && !origin) || (fetch && !result)) return MPIGX_ERR_BUFFER;
+  const bool dyn = w->flavor == MPIGX_WIN_FLAVOR_DYNAMIC;
+  const long long tdisp = dyn ? tdisp_el : tdisp_el * w->peer_du[t];
+  long long lo = 0, hi = bytes;
+  if (T.typed && (rc = rt::type_span(ttype, tcount, &lo, &hi))) return rc;
+  if (!dyn && (tdisp_el < 0 || tdisp + lo < 0 || tdisp + hi > w->peer_size[t])) return MPIGX_ERR_RMA_RANGE;
+
+  reclaim_put_tmps(w, false);
+  const char* src = (const char*)origin;
+  char* otmp = nullptr;
+  if (oc != O_NOOP && O.typed) {
+    if (!(otmp = rt::tmp_alloc(c, bytes))) return MPIGX_ERR_NO_MEM;
+    if ((rc = rt::type_pack(otype, origin, ocount, otmp, bytes, 0, c->device, c->stream))) {
+      rt::tmp_release(c, otmp);
+      return rc;
+    }
+    src = otmp;
+  }
+  char* rtmp = nullptr;
+  if (fetch && R.typed && !(rtmp = rt::tmp_alloc(c, bytes))) rc = MPIGX_ERR_NO_MEM;
+  if (!rc) rc = sync_stream(c);  // the origin buffer (and its packed copy) is final when the call is made
+  int entry = 0;
+  if (!rc && T.typed) rc = claim_type_entry(w, &entry);
+  if (!rc && T.typed) wshm(w)->ttab[c->rank][entry] = F;
+  // the last envelope posted and whether the target is known to be done with it
+  uint64_t seq = 0;
+  bool pending = false;
+  auto post_one = [&](long long k, long long m, long long res_off) {
+    const char* s = oc == O_NOOP ? nullptr : src + k * es;
+    int r;
+    if (T.typed) {
+      const TypedRef tr = {entry, tcount, k};
+      r = post(w, t, fetch ? RK_GACCT : RK_ACCT, oc, rep, tdisp, m, s, res_off, &seq, &tr);
+      if (!r) w->tt_use[entry] = {true, t, seq};
+    } else {
+      r = post(w, t, fetch ? RK_GACC : RK_ACC, oc, rep, tdisp + k * es, m, s, res_off, &seq);
+    }
+    pending = !r;
+    return r;
+  };
+  if (!rc && !fetch) rc = post_one(0, count, 0);
+  if (!rc && fetch) {
+    // Get_accumulate: chunks of one scratch slot, as acc_common's; chunk k
+    // starts at element k of the packed stream on every side
+    char* rdst = rtmp ? rtmp : (char*)result;
+    const long long per = std::max(1ll, w->slot_bytes / es);
+    const long long my_off = w->slot_bytes * c->rank;
+    for (long long k = 0; k < count && !rc; k += per) {
+      const long long m = std::min(per, count - k);
+      if ((rc = post_one(k, m, my_off))) break;
+      rc = wait_done(w, t, seq);
+      RmaEnvelope* e = &wshm(w)->box[c->rank][t].slot[seq % kRmaSlots];
+      pending = e->done.load(std::memory_order_acquire) < seq + 1;
+      if (rc) break;
+      if ((rc = pull(w, rdst + k * es, w->peer_scratch[t] + my_off, m * es))) break;
+      rc = sync_gets(w);  // the slot is reused by my next chunk
+    }
+    if (!rc && rtmp) {
+      rc = rt::type_pack(rtype, result, rcount, rtmp, bytes, 1, c->device, c->stream);
+      if (!rc) rc = sync_stream(c);  // the result is complete on return
+    }
+  }
+  if (rtmp) rt::tmp_release(c, rtmp);
+  if (otmp) {
+    if (pending) w->put_tmps.push_back({otmp, t, seq});
+    else rt::tmp_release(c, otmp);
+  }
+  return rc;
+}
+
 static int acc_common(const void* origin, int ocount, int otype, void* result, int rcount, int rtype, int t,
-                      long long tdisp_el, int tcount, int ttype, int op, mpigx_win* w, bool fetch) {
+                      long long tdisp_el, int tcount, int ttype, int op, mpigx_win* w, bool fetch,
+                      bool derived_ok = true) {
   int rc = check_win(w);
   if (rc) return rc;
   if (ocount < 0 || tcount < 0 || rcount < 0) return MPIGX_ERR_COUNT;
+  if (derived_ok && (noncontig(ttype) || (op != MPIGX_NO_OP && noncontig(otype)) || (fetch && noncontig(rtype))))
+    return acc_typed(origin, ocount, otype, result, rcount, rtype, t, tdisp_el, tcount, ttype, op, w, fetch);
   if ((rc = lower_acc_type(&ttype, &tcount)) || (op != MPIGX_NO_OP && (rc = lower_acc_type(&otype, &ocount))) ||
       (fetch && (rc = lower_acc_type(&rtype, &rcount))))
     return rc;
@@ -1159,7 +1369,7 @@ int mpigx_fetch_and_op(const void* origin_addr, void* result_addr, int datatype,
                        long long target_disp, int op, mpigx_win_t win) {
   std::lock_guard<rt::BigLock> big(rt::big_lock());  // THREAD_MULTIPLE (runtime.hpp)
   return acc_common(origin_addr, 1, datatype, result_addr, 1, datatype, target_rank, target_disp, 1, datatype, op,
-                    win, true);
+                    win, true, false);  // no non-contiguous types here (mpigx.h)
 }
 
 }  // extern "C"

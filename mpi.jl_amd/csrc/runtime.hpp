@@ -103,7 +103,17 @@ struct alignas(64) RmaEnvelope {
   long long off;
   unsigned long long raw;     // origin pointer (same-process origin)
   hipIpcMemHandle_t h;
+  // typed accumulates (RK_ACCT / RK_GACCT): the origin's type-table entry,
+  // the target instances it describes, and the index of this envelope's
+  // element 0 in their packed stream (Get_accumulate chunks)
+  int tent;
+  int tpad;
+  long long tcount;
+  long long first;
 };
+// (168 B of fields in a 192-B slot, as before the typed fields: the box and
+// WinShm keep their size)
+static_assert(sizeof(RmaEnvelope) == 192, "RMA envelope slot");
 struct RmaBox {
   RmaEnvelope slot[kRmaSlots];
 };
@@ -113,7 +123,11 @@ struct RmaBox {
 // entry (RK_PUTT: rep = entry, res_off = target instances).  The origin reuses
 // an entry only after the envelope that named it is done, so the target reads
 // it unsynchronised between `posted` and `done`.  A type of more than
-// kRmaRunCap runs is refused at the origin (MPI_ERR_TYPE).  Fixed cost:
+// kRmaRunCap runs is refused at the origin (MPI_ERR_TYPE).  Accumulate and
+// Get_accumulate through a non-contiguous target type use the same table
+// (RK_ACCT / RK_GACCT: tent = entry, tcount = target instances, first = the
+// envelope's first element in the packed stream); the target hands the runs
+// to acc_typed_kernel as arguments.  Fixed cost:
 // kMaxWins x kMaxRanks x kRmaTypeSlots entries of 2072 B = 2.1 MB of the
 // communicator's shm block, and no device memory (the target passes the runs
 // to its kernel as arguments).
@@ -410,6 +424,10 @@ int type_pack_seg(int datatype, const void* typed, int nseg, const long long* cn
 int type_span(int datatype, long long count, long long* lo, long long* hi);
 // The flattened runs of a committed type (MPIGX_ERR_TYPE past kRmaRunCap runs).
 int type_flatten(int datatype, RmaType* out);
+// MPIGX_SUCCESS when every run offset, run length, stride and the extent of a
+// committed type are multiples of `es` (an element of that size never
+// straddles two runs or instances), else MPIGX_ERR_TYPE.
+int type_elem_aligned(int datatype, long long es);
 // `bytes` packed bytes from src through stype to dst through dtype (copy.hip
 // typed_xfer_kernel); flat_xfer: contiguous src, destination type as runs.
 int type_xfer(int stype, const void* src, int dtype, void* dst, long long bytes, int device, hipStream_t s);

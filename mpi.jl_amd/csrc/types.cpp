@@ -336,6 +336,15 @@ int type_flatten(int h, RmaType* out) {
   return MPIGX_SUCCESS;
 }
 
+int type_elem_aligned(int h, long long es) {
+  DType f;
+  if (!flat_of(h, &f, true) || es <= 0) return MPIGX_ERR_TYPE;
+  if ((f.ub - f.lb) % es) return MPIGX_ERR_TYPE;
+  for (const TypeRun& r : f.runs)
+    if (r.off % es || r.len % es || (r.n > 1 && r.stride % es)) return MPIGX_ERR_TYPE;
+  return MPIGX_SUCCESS;
+}
+
 namespace {
 unsigned long long align_bits(const std::vector<TypeRun>& runs, long long size, long long extent) {
   unsigned long long g = (unsigned long long)extent | (unsigned long long)size;

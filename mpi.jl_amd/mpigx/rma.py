@@ -422,33 +422,47 @@ def Fetch_and_op(sourceval, returnval, target_rank, target_disp, op, win):
         rb.reshape(-1)[:] = res.cpu().numpy()
 
 
-def Accumulate(origin_buffer, count, target_rank, target_disp, op, win):
-    """onesided.jl:197-206."""
-    dt = _dtype_val(origin_buffer)
+def _acc_sides(origin_buffer, result_buffer, count, target):
+    """(count, engine handle, host handle) of the origin, result and target
+    side of Accumulate / Get_accumulate.  An MPI.Buffer carries its own count
+    and datatype (a vector, a subarray ...), an array goes by `count` and its
+    element type; `target` as in _xfer_args (default: the origin's)."""
+    from .api import Buffer
+    o = _operand(origin_buffer, count)
+    r = _operand(result_buffer, count) if result_buffer is not None else None
+    t = o if target is None else _operand(target if isinstance(target, Buffer) else Buffer(None, target[0], target[1]))
+    return o, r, t
+
+
+def Accumulate(origin_buffer, count, target_rank, target_disp, op, win, target=None):
+    """onesided.jl:197-206.  `origin_buffer` may be an MPI.Buffer (count +
+    datatype, `count` is then ignored); `target`: see _xfer_args."""
+    (oc, odt, ohost), _, (tc, tdt, thost) = _acc_sides(origin_buffer, None, count, target)
     opv = _opval(op, origin_buffer)
     if _host(win):
-        _hcheck(hostmpi.lib().MPI_Accumulate(_hptr(_unwrap(origin_buffer)), int(count), dt, int(target_rank),
-                                             _aint(target_disp), int(count), dt, opv, win.val))
+        _hcheck(hostmpi.lib().MPI_Accumulate(_hptr(_unwrap(origin_buffer)), oc, ohost, int(target_rank),
+                                             _aint(target_disp), tc, thost, opv, win.val))
         return
     src = _to_dev(win, origin_buffer)
-    _dev_call(win, "mpigx_accumulate", _dptr(src), int(count), dt, int(target_rank),
-              ctypes.c_longlong(int(target_disp)), int(count), dt, opv, win.val)
+    _dev_call(win, "mpigx_accumulate", _dptr(src), oc, odt, int(target_rank),
+              ctypes.c_longlong(int(target_disp)), tc, tdt, opv, win.val)
 
 
-def Get_accumulate(origin_buffer, result_buffer, count, target_rank, target_disp, op, win):
-    """onesided.jl:208-219."""
+def Get_accumulate(origin_buffer, result_buffer, count, target_rank, target_disp, op, win, target=None):
+    """onesided.jl:208-219.  `origin_buffer` and `result_buffer` may be
+    MPI.Buffers (count + datatype); `target`: see _xfer_args."""
     assert _unwrap(origin_buffer).dtype == _unwrap(result_buffer).dtype
-    dt = _dtype_val(origin_buffer)
+    (oc, odt, ohost), (rc, rdt, rhost), (tc, tdt, thost) = _acc_sides(origin_buffer, result_buffer, count, target)
     opv = _opval(op, origin_buffer)
     if _host(win):
-        _hcheck(hostmpi.lib().MPI_Get_accumulate(_hptr(_unwrap(origin_buffer)), int(count), dt,
-                                                 _hptr(_unwrap(result_buffer)), int(count), dt, int(target_rank),
-                                                 _aint(target_disp), int(count), dt, opv, win.val))
+        _hcheck(hostmpi.lib().MPI_Get_accumulate(_hptr(_unwrap(origin_buffer)), oc, ohost,
+                                                 _hptr(_unwrap(result_buffer)), rc, rhost, int(target_rank),
+                                                 _aint(target_disp), tc, thost, opv, win.val))
         return
     src = _to_dev(win, origin_buffer)
     rb = _unwrap(result_buffer)
     res = _to_dev(win, rb)
-    _dev_call(win, "mpigx_get_accumulate", _dptr(src), int(count), dt, _dptr(res), int(count), dt, int(target_rank),
-              ctypes.c_longlong(int(target_disp)), int(count), dt, opv, win.val)
+    _dev_call(win, "mpigx_get_accumulate", _dptr(src), oc, odt, _dptr(res), rc, rdt, int(target_rank),
+              ctypes.c_longlong(int(target_disp)), tc, tdt, opv, win.val)
     if isinstance(rb, np.ndarray):
         rb.reshape(-1)[:] = res.cpu().numpy()

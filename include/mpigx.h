@@ -281,6 +281,35 @@ int mpigx_allgatherv(const void *sendbuf, int sendcount, int sendtype, void *rec
 int mpigx_alltoallv(const void *sendbuf, const int *sendcounts, const int *sdispls, int sendtype,
                     void *recvbuf, const int *recvcounts, const int *rdispls, int recvtype,
                     mpigx_comm_t comm);
+/* MPI_Alltoallw (MPI.jl v0.14.2 wraps no Alltoallw; MPICH 3.3.2 semantics):
+ * a datatype and a displacement per peer.  The eight arrays are host int[n];
+ * sdispls / rdispls are in BYTES from the buffer pointer; sendtypes[q] /
+ * recvtypes[q] may be any predefined type or any committed libmpigx type,
+ * different for every q.  Block q of the send side is sendcounts[q] instances
+ * of sendtypes[q] at sendbuf + sdispls[q]; it travels as the packed stream of
+ * that type map and is stored on rank q through recvtypes[me] at
+ * recvbuf + rdispls[me].  Zero counts are legal anywhere; a rank that sends
+ * or receives nothing still takes part.  sendbuf == MPIGX_IN_PLACE (MPI-2.2):
+ * the three send arrays are ignored (may be NULL) and block q is taken from,
+ * and replaced in, recvbuf through recvcounts[q] / recvtypes[q] / rdispls[q].
+ * A side whose non-empty blocks are all predefined or contiguous is moved in
+ * place; any other side is packed (unpacked) by ONE segw_pack_kernel launch
+ * in which each block has its own type map and unit width.
+ * Write footprint: no byte of recvbuf outside the type maps of its non-empty
+ * blocks is written (holes inside instances, gaps between blocks, bytes
+ * before the lowest and after the highest displacement); sendbuf is never
+ * written.
+ * Refused before anything is packed or exchanged, both buffers untouched:
+ * a NULL count, displacement or type array (the send arrays under IN_PLACE
+ * excepted) MPIGX_ERR_ARG; a negative count MPIGX_ERR_COUNT; an unknown,
+ * freed or uncommitted type in any slot, even one of count 0,
+ * MPIGX_ERR_TYPE; a NULL buffer with a non-zero total MPIGX_ERR_BUFFER; a
+ * NULL communicator MPIGX_ERR_COMM.  A size mismatch between the two ends of
+ * a block is an erroneous program and is not detected.  Communicators of up
+ * to MPIGX_MAX_RANKS; n = 1 is a local typed copy. */
+int mpigx_alltoallw(const void *sendbuf, const int *sendcounts, const int *sdispls,
+                    const int *sendtypes, void *recvbuf, const int *recvcounts,
+                    const int *rdispls, const int *recvtypes, mpigx_comm_t comm);
 /* MPI_Reduce   — collective.jl:605-618 (IN_PLACE at root; recvbuf ignored
  * (may be NULL) elsewhere) */
 int mpigx_reduce(const void *sendbuf, void *recvbuf, int count, int datatype, int op,

@@ -73,6 +73,16 @@ int mpigx_mix_probe(const void *const *in, int nin, long long bytes, void *out, 
 int mpigx_pack_segments(const void *typed, int datatype, int nseg, const long long *counts,
                         const long long *displs, const long long *offsets, void *packed, int unpack,
                         void *stream);
+/* Alltoallw's segmented pack / unpack on its own (copy.hip
+ * segw_pack_kernel): segment j = counts[j] instances of datatypes[j] (any
+ * predefined or committed type) whose first lies at typed + displs[j] BYTES,
+ * packed at packed + offsets[j] (unpack != 0: the reverse).  w_out[j]
+ * receives the unit width in bytes chosen for segment j (0 for an empty one;
+ * w_out may be NULL).  nseg <= MPIGX_MAX_RANKS, one launch on `stream`,
+ * blocking. */
+int mpigx_pack_segments_w(const void *typed, int nseg, const int *datatypes, const long long *counts,
+                          const long long *displs, const long long *offsets, void *packed, int unpack,
+                          int *w_out, void *stream);
 /* Zero-copy paths (user buffers mapped by the peers over IPC): how many
  * launches ran on a cached view without any host exchange, and how many
  * host exchanges of buffer registrations there were.  Diagnostic. */

@@ -577,6 +577,75 @@ hipError_t launch_seg_pack(hipStream_t s, const SegPackArgs& in) {
   return hipGetLastError();
 }
 
+// Segmented pack / unpack with a type map per segment (typed.hpp SegWArgs):
+// every block of an Alltoallw side in one launch.  Block b serves segment j
+// with blk0[j] <= b < blk0[j+1] and the share [k*share, (k+1)*share) of that
+// segment's units; the segment's fields are block-uniform, so the switch on
+// its unit width does not diverge.
+template <int W>
+__device__ __forceinline__ void segw_move(char* typed, char* contig, const SegW& S, long long u0, long long u1,
+                                          int unpack) {
+  using V = typename UnitOf<W>::type;
+  for (long long u = u0 + threadIdx.x; u < u1; u += blockDim.x) {
+    const long long p = u * W;
+    const long long t = typed_off(S.runs, S.pfx, S.nruns, S.size, S.extent, p);
+    if (unpack) *reinterpret_cast<V*>(typed + t) = *reinterpret_cast<const V*>(contig + p);
+    else *reinterpret_cast<V*>(contig + p) = *reinterpret_cast<const V*>(typed + t);
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void segw_pack_kernel(SegWArgs A) {
+  pull_acquire(A.coherent);
+  const int b = blockIdx.x;
+  int j = 0;
+  while (j + 1 < A.nseg && b >= A.blk0[j + 1]) ++j;
+  const SegW S = A.seg[j];
+  const long long g = A.blk0[j + 1] - A.blk0[j], k = b - A.blk0[j];
+  const long long share = (S.units + g - 1) / g;
+  const long long u0 = lmin(k * share, S.units), u1 = lmin(u0 + share, S.units);
+  char* typed = A.typed + S.t_off;
+  char* contig = A.contig + S.c_off;
+  switch (S.w) {
+    case 16: segw_move<16>(typed, contig, S, u0, u1, A.unpack); break;
+    case 8: segw_move<8>(typed, contig, S, u0, u1, A.unpack); break;
+    case 4: segw_move<4>(typed, contig, S, u0, u1, A.unpack); break;
+    case 2: segw_move<2>(typed, contig, S, u0, u1, A.unpack); break;
+    default: segw_move<1>(typed, contig, S, u0, u1, A.unpack); break;
+  }
+  pull_release(A.coherent);
+}
+
+// Deals kSegGrid blocks to the non-empty segments in proportion to their
+// BYTES (their units are of different widths): at least one block each, never
+// more than a segment's units fill, none for an empty segment.  Nothing is
+// launched when every segment is empty.
+hipError_t launch_segw_pack(hipStream_t s, const SegWArgs& in) {
+  SegWArgs a = in;
+  if (a.nseg < 0 || a.nseg > kMaxRanks) return hipErrorInvalidValue;
+  long long total = 0, want = 0;
+  for (int j = 0; j < a.nseg; ++j) {
+    if (a.seg[j].units <= 0) continue;
+    total += a.seg[j].units * a.seg[j].w;
+    want += (a.seg[j].units + kThreads - 1) / kThreads;
+  }
+  if (total <= 0) return hipSuccess;
+  const long long G = want > kSegGrid ? kSegGrid : want;
+  a.blk0[0] = 0;
+  for (int j = 0; j < a.nseg; ++j) {
+    long long g = 0;
+    if (a.seg[j].units > 0) {
+      g = (long long)((double)G * (double)(a.seg[j].units * a.seg[j].w) / (double)total);
+      const long long need = (a.seg[j].units + kThreads - 1) / kThreads;
+      g = g > need ? need : g;
+      g = g < 1 ? 1 : g;
+    }
+    a.blk0[j + 1] = a.blk0[j] + (int)g;
+  }
+  for (int j = a.nseg; j < kMaxRanks; ++j) a.blk0[j + 1] = a.blk0[a.nseg];
+  hipLaunchKernelGGL(segw_pack_kernel, dim3((unsigned)a.blk0[a.nseg]), dim3(kThreads), 0, s, a);
+  return hipGetLastError();
+}
+
 // Typed -> typed transfer (typed.hpp TypedXferArgs): unit u of the packed
 // stream is read at src through the source map and written at dst through the
 // destination map, one pass.  The destination is always local memory; the

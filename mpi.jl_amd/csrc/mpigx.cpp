@@ -3942,6 +3942,109 @@ int mpigx_alltoallv(const void* sendbuf, const int* sendcounts, const int* sdisp
   return vexchange(c, s);
 }
 
+// One side of Alltoallw: block q has its own datatype, count and BYTE
+// displacement.  A side whose every non-empty block is predefined or
+// contiguous is addressed in place (block q = len[q] bytes at dsp[q]).  Any
+// other side goes through a pooled temporary in which block q's packed bytes
+// start at the 16-B-aligned prefix off[q], and ONE segw_pack_kernel launch
+// packs (before the exchange) or unpacks (after it) every block, the
+// contiguous ones as single-run maps.
+struct WSide {
+  mpigx_comm* c = nullptr;
+  int nseg = 0;
+  bool pack = false;
+  char* user = nullptr;  // the typed buffer
+  char* buf = nullptr;   // what vexchange addresses: user, or the temporary
+  char* tmp = nullptr;
+  long long total = 0;   // packed bytes, each block rounded up to 16
+  int type[kMaxRanks] = {};
+  long long cnt[kMaxRanks] = {}, dsp[kMaxRanks] = {}, off[kMaxRanks] = {}, len[kMaxRanks] = {};
+  ~WSide() {
+    if (tmp) tmp_put(c, tmp, 0);
+  }
+};
+
+// Checks only (nothing is allocated): every type slot must name a predefined
+// or committed type, even where its count is 0.
+static int wside_check(mpigx_comm* c, WSide* v, const void* user, int nseg, const int* counts, const int* displs,
+                       const int* types) {
+  v->c = c;
+  v->nseg = nseg;
+  v->user = (char*)user;
+  for (int q = 0; q < nseg; ++q)
+    if (counts[q] < 0) return MPIGX_ERR_COUNT;
+  for (int q = 0; q < nseg; ++q) {
+    rt::TypeDesc d;
+    if (rt::type_info(types[q], &d)) return MPIGX_ERR_TYPE;
+    v->type[q] = types[q];
+    v->cnt[q] = counts[q];
+    v->dsp[q] = displs[q];
+    v->len[q] = v->cnt[q] * d.size;
+    if (v->len[q] && !d.contig) v->pack = true;
+    v->total += (v->len[q] + 15) & ~15ll;
+  }
+  if (v->total && !user) return MPIGX_ERR_BUFFER;
+  return MPIGX_SUCCESS;
+}
+
+static int wside_place(WSide* v) {
+  long long at = 0;
+  for (int q = 0; q < v->nseg; ++q) {
+    v->off[q] = v->pack ? at : v->dsp[q];
+    at += (v->len[q] + 15) & ~15ll;
+  }
+  v->buf = v->user;
+  if (v->pack) {
+    if (!(v->tmp = tmp_get(v->c, v->total > 16 ? v->total : 16))) return MPIGX_ERR_NO_MEM;
+    v->buf = v->tmp;
+  }
+  return MPIGX_SUCCESS;
+}
+
+static int wside_move(WSide* v, int unpack) {
+  if (!v->pack) return MPIGX_SUCCESS;
+  rt::SegWSpec segs[kMaxRanks];
+  for (int q = 0; q < v->nseg; ++q) segs[q] = {v->type[q], v->cnt[q], v->dsp[q], v->off[q]};
+  const int rc = rt::type_pack_segw(v->user, v->nseg, segs, v->tmp, unpack, v->c->device, v->c->stream, nullptr);
+  if (!rc) v->c->unflagged = true;  // the final finish() drains the stream
+  return rc;
+}
+
+// MPI_Alltoallw: a datatype and a byte displacement per peer; MPI-2.2
+// IN_PLACE takes the send layout from the receive arguments.
+int mpigx_alltoallw(const void* sendbuf, const int* sendcounts, const int* sdispls, const int* sendtypes,
+                    void* recvbuf, const int* recvcounts, const int* rdispls, const int* recvtypes, mpigx_comm_t c) {
+  int rc = check_comm(c);
+  if (rc) return rc;
+  const int n = c->n, r = c->rank;
+  const bool inplace = sendbuf == MPIGX_IN_PLACE;
+  if (!recvcounts || !rdispls || !recvtypes) return MPIGX_ERR_ARG;
+  if (!inplace && (!sendcounts || !sdispls || !sendtypes)) return MPIGX_ERR_ARG;
+  WSide S, R;
+  if ((rc = wside_check(c, &R, recvbuf, n, recvcounts, rdispls, recvtypes))) return rc;
+  if (!inplace && (rc = wside_check(c, &S, sendbuf, n, sendcounts, sdispls, sendtypes))) return rc;
+  if ((rc = wside_place(&R))) return rc;
+  if (!inplace && (rc = wside_place(&S))) return rc;
+  WSide& O = inplace ? R : S;
+  VSpec s;
+  s.ncopy = n;
+  for (int q = 0; q < n; ++q) {
+    s.c_slot[q] = q;
+    s.c_src[q] = O.off[q];
+    s.c_len[q] = O.len[q];
+    s.p_len[q] = R.len[q];
+    s.p_slot[q] = r;
+    s.p_dst[q] = R.off[q];
+  }
+  s.send = O.buf;
+  s.recv = R.buf;
+  rc = wside_move(&O, 0);
+  if (!rc) rc = vexchange(c, s);
+  if (!rc) rc = wside_move(&R, 1);
+  if (!rc) rc = finish(c);
+  return rc;
+}
+
 // ---------------------------------------------------------------------------
 // User-defined ops (operators.jl:56-88 OpWrapper, MPI_Op_create; SURVEY §8f
 // row 4).  Two kinds of callback:

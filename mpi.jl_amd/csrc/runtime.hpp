@@ -420,6 +420,17 @@ int type_pack(int datatype, const void* typed, long long count, void* contig, lo
 // packed at contig + c_off[j] (unpack = 1: the reverse); nseg <= kMaxRanks.
 int type_pack_seg(int datatype, const void* typed, int nseg, const long long* cnt, const long long* dsp,
                   const long long* c_off, void* contig, int unpack, int device, hipStream_t s);
+// The blocks of an Alltoallw side in one launch (copy.hip segw_pack_kernel):
+// segment j = `count` instances of ITS `type` (any predefined or committed
+// one) from typed + t_off bytes, packed at contig + c_off (unpack = 1: the
+// reverse).  The unit width is chosen per segment (unit_of's rule) and
+// returned in w_out[j] (0 for an empty segment) when w_out is given.
+struct SegWSpec {
+  int type;
+  long long count, t_off, c_off;
+};
+int type_pack_segw(const void* typed, int nseg, const SegWSpec* segs, void* contig, int unpack, int device,
+                   hipStream_t s, int* w_out);
 // True bounds [lo, hi) of `count` instances, in bytes from the buffer pointer.
 int type_span(int datatype, long long count, long long* lo, long long* hi);
 // The flattened runs of a committed type (MPIGX_ERR_TYPE past kRmaRunCap runs).

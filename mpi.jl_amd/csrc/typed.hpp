@@ -34,6 +34,34 @@ struct SegPackArgs {
   long long units[kMaxRanks];
 };
 
+// Segmented pack / unpack in which every segment has a type map, a unit width
+// and byte offsets of its own (Alltoallw: segment q = the block of peer q, in
+// the datatype of that peer).  Segment j = `units` units of `w` bytes whose
+// first instance lies at typed + t_off (bytes) and whose packed bytes start at
+// contig + c_off; `nruns` = 0 is a contiguous block (predefined or contiguous
+// type), otherwise the map is typed_off's over runs / pfx (the per-type device
+// copies).  Segment j owns blocks [blk0[j], blk0[j+1]), dealt in proportion to
+// its bytes; all threads of a block serve one segment, so the width is
+// block-uniform.  64 B per segment: 1.1 KiB of kernel arguments at 16.
+struct SegW {
+  const TypeRun* runs;
+  const long long* pfx;
+  long long size, extent;
+  long long t_off, c_off;
+  long long units;
+  int nruns;
+  int w;
+};
+struct SegWArgs {
+  char* typed;
+  char* contig;
+  int unpack;
+  int coherent;
+  int nseg;
+  int blk0[kMaxRanks + 1];
+  SegW seg[kMaxRanks];
+};
+
 // One side of a typed transfer: `nruns` = 0 is a contiguous stream (packed
 // byte p lives at p), otherwise instances `extent` apart of `size` packed
 // bytes each, mapped through runs / pfx as in PackArgs.
@@ -61,6 +89,7 @@ struct TypedXferArgs {
 };
 
 hipError_t launch_seg_pack(hipStream_t s, const SegPackArgs& a);
+hipError_t launch_segw_pack(hipStream_t s, const SegWArgs& a);
 hipError_t launch_typed_xfer(hipStream_t s, const TypedXferArgs& a);
 
 }  // namespace mpigx

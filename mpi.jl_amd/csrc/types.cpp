@@ -315,6 +315,55 @@ int type_pack_seg(int h, const void* typed, int nseg, const long long* cnt, cons
   return MPIGX_SUCCESS;
 }
 
+int type_pack_segw(const void* typed, int nseg, const SegWSpec* segs, void* contig, int unpack, int device,
+                   hipStream_t s, int* w_out) {
+  if (nseg < 0 || nseg > kMaxRanks) return MPIGX_ERR_ARG;
+  SegWArgs a;
+  memset(&a, 0, sizeof a);
+  bool any = false;
+  for (int j = 0; j < nseg; ++j) {
+    const SegWSpec& q = segs[j];
+    SegW& S = a.seg[j];
+    TypeDesc d;
+    if (type_info(q.type, &d)) return MPIGX_ERR_TYPE;
+    if (w_out) w_out[j] = 0;
+    const long long bytes = q.count * d.size;
+    if (bytes <= 0) continue;
+    any = true;
+    S.size = d.size;
+    S.extent = d.extent;
+    S.t_off = q.t_off;
+    S.c_off = q.c_off;
+    const char* t0 = (const char*)typed + q.t_off;
+    const char* c0 = (const char*)contig + q.c_off;
+    if (d.contig) {
+      // predefined or contiguous: bytes at their displacement, no run table
+      const unsigned long long g = (unsigned long long)(uintptr_t)t0 | (unsigned long long)(uintptr_t)c0 |
+                                   (unsigned long long)bytes | 16ull;
+      S.w = (int)(g & (~g + 1));
+    } else {
+      DType* t = lookup(q.type);
+      const int rc = device_runs(t, device, &S.runs, &S.pfx);
+      if (rc) return rc;
+      S.nruns = (int)t->runs.size();
+      S.w = unit_of(*t, t0, c0, bytes);
+    }
+    S.units = bytes / S.w;
+    if (w_out) w_out[j] = S.w;
+  }
+  if (!any) return MPIGX_SUCCESS;
+  a.nseg = nseg;
+  a.unpack = unpack;
+  a.coherent = pull_fences();
+  a.typed = (char*)typed;
+  a.contig = (char*)contig;
+  if (launch_segw_pack(s, a) != hipSuccess) {
+    (void)hipGetLastError();
+    return MPIGX_ERR_INTERN;
+  }
+  return MPIGX_SUCCESS;
+}
+
 int type_span(int h, long long count, long long* lo, long long* hi) {
   DType f;
   if (!flat_of(h, &f, true)) return MPIGX_ERR_TYPE;
@@ -669,6 +718,26 @@ int mpigx_pack_segments(const void* typed, int datatype, int nseg, const long lo
   if (hipGetDevice(&dev) != hipSuccess) return MPIGX_ERR_INTERN;
   const int rc = rt::type_pack_seg(datatype, typed, nseg, counts, displs, offsets, packed, unpack ? 1 : 0, dev,
                                    (hipStream_t)stream);
+  if (rc) return rc;
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
+    (void)hipGetLastError();
+    return MPIGX_ERR_INTERN;
+  }
+  return MPIGX_SUCCESS;
+}
+
+int mpigx_pack_segments_w(const void* typed, int nseg, const int* datatypes, const long long* counts,
+                          const long long* displs, const long long* offsets, void* packed, int unpack, int* w_out,
+                          void* stream) {
+  if (nseg < 0 || nseg > kMaxRanks || (nseg && (!datatypes || !counts || !displs || !offsets))) return MPIGX_ERR_ARG;
+  rt::SegWSpec segs[kMaxRanks];
+  for (int j = 0; j < nseg; ++j) {
+    if (counts[j] < 0) return MPIGX_ERR_COUNT;
+    segs[j] = {datatypes[j], counts[j], displs[j], offsets[j]};
+  }
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return MPIGX_ERR_INTERN;
+  const int rc = rt::type_pack_segw(typed, nseg, segs, packed, unpack ? 1 : 0, dev, (hipStream_t)stream, w_out);
   if (rc) return rc;
   if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
     (void)hipGetLastError();

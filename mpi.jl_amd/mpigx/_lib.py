@@ -71,6 +71,8 @@ PROTOTYPES = {
     "mpigx_mix_probe": (c_int, [ctypes.POINTER(c_void_p), c_int, c_longlong, c_void_p, c_void_p]),
     "mpigx_pack_segments": (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_longlong), ctypes.POINTER(c_longlong),
                                     ctypes.POINTER(c_longlong), c_void_p, c_int, c_void_p]),
+    "mpigx_pack_segments_w": (c_int, [c_void_p, c_int, _IP, ctypes.POINTER(c_longlong), ctypes.POINTER(c_longlong),
+                                      ctypes.POINTER(c_longlong), c_void_p, c_int, _IP, c_void_p]),
     "mpigx_barrier": (c_int, [c_void_p]),
     "mpigx_bcast": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "mpigx_allgather": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
@@ -81,6 +83,7 @@ PROTOTYPES = {
     "mpigx_scatterv": (c_int, [c_void_p, _IP, _IP, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mpigx_allgatherv": (c_int, [c_void_p, c_int, c_int, c_void_p, _IP, _IP, c_int, c_void_p]),
     "mpigx_alltoallv": (c_int, [c_void_p, _IP, _IP, c_int, c_void_p, _IP, _IP, c_int, c_void_p]),
+    "mpigx_alltoallw": (c_int, [c_void_p, _IP, _IP, _IP, c_void_p, _IP, _IP, _IP, c_void_p]),
     "mpigx_reduce": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mpigx_allreduce": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mpigx_scan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

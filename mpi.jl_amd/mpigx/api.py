@@ -1006,6 +1006,64 @@ def Alltoallv(sendbuf, scounts, rcounts, comm):
     return Alltoallv_(sendbuf, _empty_like(sendbuf, sum(rcounts)), scounts, rcounts, comm)
 
 
+def _nbytes(buf):
+    b = _unwrap(buf)
+    return b.nbytes if isinstance(b, np.ndarray) else b.numel() * b.element_size()
+
+
+def _assert_spans(buf, counts, displs, types):
+    """Alltoallw's analogue of @assert_minlength: the true bounds of every
+    non-empty block (displacement in bytes, its own datatype) lie inside the
+    buffer."""
+    room = _nbytes(buf)
+    for q, (cnt, dsp, T) in enumerate(zip(counts, displs, types)):
+        size, lb, ext = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_longlong(0)
+        tlb, text = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        _check(lib().mpigx_type_size_x(T.val, ctypes.byref(size)))
+        if int(cnt) <= 0 or size.value == 0:
+            continue
+        _check(lib().mpigx_type_get_extent(T.val, ctypes.byref(lb), ctypes.byref(ext)))
+        _check(lib().mpigx_type_get_true_extent(T.val, ctypes.byref(tlb), ctypes.byref(text)))
+        last = (int(cnt) - 1) * ext.value
+        lo = int(dsp) + tlb.value + min(0, last)
+        hi = int(dsp) + tlb.value + text.value + max(0, last)
+        assert 0 <= lo and hi <= room, f"block {q}: bytes [{lo}, {hi}) outside a buffer of {room} bytes"
+
+
+def Alltoallw_(sendbuf, scounts, sdispls, stypes, recvbuf, rcounts, rdispls, rtypes, comm):
+    """MPI_Alltoallw (MPI.jl v0.14.2 has no wrapper; the argument list is
+    MPI's): block q of the send side is scounts[q] instances of stypes[q] at
+    byte displacement sdispls[q] of sendbuf, and block q of the receive side
+    rcounts[q] instances of rtypes[q] at byte displacement rdispls[q] of
+    recvbuf.  The buffers are plain arrays / tensors addressed as bytes; the
+    types are anything `Datatype()` accepts.  `sendbuf` may be IN_PLACE, and
+    the three send arguments may then be None."""
+    n = Comm_size(comm)
+    rtypes = [Datatype(t) for t in rtypes]
+    assert len(rcounts) == len(rdispls) == len(rtypes) == n
+    _assert_spans(recvbuf, rcounts, rdispls, rtypes)
+    host = _is_host(recvbuf)
+    if sendbuf is IN_PLACE:
+        send = (None, None, None)
+    else:
+        stypes = [Datatype(t) for t in stypes]
+        assert len(scounts) == len(sdispls) == len(stypes) == n
+        _assert_spans(sendbuf, scounts, sdispls, stypes)
+        send = (_cints(scounts), _cints(sdispls), _cints([t.host if host else t.val for t in stypes]))
+    recv = (_cints(rcounts), _cints(rdispls), _cints([t.host if host else t.val for t in rtypes]))
+    if host:
+        if comm.host is None:
+            raise TypeError("host buffers need host libmpi (start the ranks with mpiexec)")
+        rc = hostmpi.lib().MPI_Alltoallw(_ptr(sendbuf), *send, _ptr(recvbuf), *recv, comm.host)
+    else:
+        if not comm.val:
+            raise TypeError("device buffers need a ROCm device")
+        _stream(comm)
+        rc = lib().mpigx_alltoallw(_ptr(sendbuf), *send, _ptr(recvbuf), *recv, comm.val)
+    _check(rc)
+    return recvbuf
+
+
 def _scalar_ref(obj, comm):
     """`Ref(object)` of the scalar forms: a 1-element host array when host
     libmpi is up (as in MPI.jl), else a 1-element device tensor."""

@@ -1,5 +1,5 @@
-"""Pack gen_redscat_golden.c's dumps into tests/golden/redscat_golden.npz (n <= 5)
-and redscat_golden_n6_n8.npz (one uint8 array per case, `<id>`: every rank's
+"""Pack gen_redscat_golden.c's dumps into tests/golden/redscat_golden.npz (n <= 5),
+redscat_golden_n6_n8.npz and redscat_golden_n7.npz (one uint8 array per case, `<id>`: every rank's
 output bytes in rank order, each in full or at the case's spans; tests/redscat_model.py split_outputs cuts it) +
 redscat_golden_manifest.json.  Load with numpy.load (no pickle).
 
@@ -40,6 +40,9 @@ def main(raw, dest):
         if fn.startswith("manifest_redscat_") and fn.endswith(".jsonl"):
             with open(os.path.join(raw, fn)) as f:
                 cases += [json.loads(l) for l in f if l.strip()]
+    # the manifest follows the files (tests/redscat_model.py GOLDEN_FILES): a world size recorded
+    # later gets a file of its own and its cases go to the end, behind the ones already there
+    cases.sort(key=lambda c: next(i for i, (_, keep) in enumerate(R.GOLDEN_FILES) if c["n"] in keep))
     arrays = {}
     for c in cases:
         arrays[c["id"]] = [np.fromfile(os.path.join(raw, f"{c['id']}.r{r}.bin"), dtype=np.uint8)
@@ -48,7 +51,7 @@ def main(raw, dest):
     if weak:
         raise SystemExit(f"fixtures that do not discriminate: {weak}")
     arrays = {k: np.concatenate(v) for k, v in arrays.items()}
-    # two files, by world size, each under the repository's 1 MiB per file
+    # one file per group of world sizes, each under the repository's 1 MiB per file
     for name, keep in R.GOLDEN_FILES:
         part = {c["id"]: arrays[c["id"]] for c in cases if c["n"] in keep}
         np.savez_compressed(os.path.join(dest, name), **part)

@@ -1,4 +1,5 @@
 """Loader for the MPICH golden fixtures (tests/golden/, made by make_golden.sh)."""
+import glob
 import json
 import os
 
@@ -7,11 +8,45 @@ import numpy as np
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+# world sizes recorded later, in files of their own (tests/golden/pack_golden.py OWN_FILES)
+OWN_FILES = (7,)
+
+
+def golden_files():
+    """The .npz files load() reads, the first fixture first."""
+    files = [os.path.join(HERE, "mpich_golden.npz")]
+    for n in OWN_FILES:
+        parts = sorted(glob.glob(os.path.join(HERE, f"mpich_golden_n{n}_[a-z].npz")))
+        assert parts, f"no mpich_golden_n{n}_*.npz"
+        files += parts
+    return files
+
+
+class Arrays:
+    """Read-only union of .npz files: arrays[key], loaded on first use."""
+
+    def __init__(self, paths):
+        self._of = {}
+        for z in (np.load(p, allow_pickle=False) for p in paths):
+            for k in z.files:
+                assert k not in self._of, k
+                self._of[k] = z
+        self.files = list(self._of)
+
+    def __getitem__(self, key):
+        return self._of[key][key]
+
+    def __contains__(self, key):
+        return key in self._of
+
+
 def load():
-    with open(os.path.join(HERE, "mpich_golden_manifest.json")) as f:
-        cases = json.load(f)
-    arrays = np.load(os.path.join(HERE, "mpich_golden.npz"), allow_pickle=False)
-    return cases, arrays
+    """(cases, arrays): every manifest in turn, and the arrays of every file."""
+    cases = []
+    for name in ["mpich_golden_manifest.json"] + [f"mpich_golden_n{n}_manifest.json" for n in OWN_FILES]:
+        with open(os.path.join(HERE, name)) as f:
+            cases += json.load(f)
+    return cases, Arrays(golden_files())
 
 
 def op_type_matrix():

@@ -159,7 +159,8 @@ def case_inputs(case):
 
 
 # the recorded outputs, split by world size (tests/golden/pack_redscat_golden.py)
-GOLDEN_FILES = (("redscat_golden.npz", (1, 2, 3, 4, 5)), ("redscat_golden_n6_n8.npz", (6, 8)))
+GOLDEN_FILES = (("redscat_golden.npz", (1, 2, 3, 4, 5)), ("redscat_golden_n6_n8.npz", (6, 8)),
+                ("redscat_golden_n7.npz", (7,)))
 
 
 def load_golden():

@@ -5,6 +5,15 @@ Runs every MPICH golden case recorded at this world size through libmpigx's
 C ABI on device buffers (both algorithms, in-place forms, both reduce
 orders), plus larger seeded cases checked against the oracle, and exits
 non-zero on any mismatch.  Launched by tests/test_collectives_gpu.py.
+
+GOLDEN_PASSES lists the passes of one launch: "staged", "zc" (every size
+through the zero-copy paths, MPIGX_ZC_MIN=1 MPIGX_ZC_REQUIRE=1) or
+"staged,zc".  A pass whose path the launch's environment already selects runs
+on COMM_WORLD; the zero-copy pass after a staged one runs on a Comm_dup made
+once every rank has put the two settings into its environment (a communicator
+reads its path-selecting settings when it is created).  Each pass runs the
+phases its own launch would and prints its own summary line.  Without
+GOLDEN_PASSES the launch is one pass, "zc" if MPIGX_ZC_MIN is set.
 """
 import ctypes
 import json
@@ -26,13 +35,15 @@ from oracle import mpich_model as M  # noqa: E402
 
 IN_PLACE = ctypes.c_void_p(-1 & ((1 << 64) - 1))
 # Allreduce algorithms to run every case through; the push two-shot needs the
-# zero-copy mapping, so it joins when the zero-copy test forces that path
+# zero-copy mapping, so it joins in the zero-copy pass (Runner.ar_algos)
 # "ll": LL up to its capacity (MPIGX_LL_MAX), the default choice above it;
 # "ll2": the LL two-shot where a chunk fits half an LL slot;
 # "oneshot"/"twoshot" force the staged algorithms
 # "pull_generic": the zero-copy pull two-shot through the all-modes fold
 # kernel instead of its dedicated kernel (ar_zc_kernel)
-AR_ALGOS = ("ll", "ll2", "oneshot", "twoshot") + (("push", "pull_generic", "pullpush") if os.environ.get("MPIGX_ZC_MIN") else ())
+STAGED_ALGOS = ("ll", "ll2", "oneshot", "twoshot")
+ZC_ALGOS = STAGED_ALGOS + ("push", "pull_generic", "pullpush")
+ZC_ENV = {"MPIGX_ZC_MIN": "1", "MPIGX_ZC_REQUIRE": "1"}
 
 
 # device buffers made for the current call: P(dev(x)) hands out a raw
@@ -59,8 +70,11 @@ def host(t, dt):
 
 
 class Runner:
-    def __init__(self, comm):
+    def __init__(self, comm, zc=False):
+        """zc: comm was created with MPIGX_ZC_MIN set (the zero-copy pass)."""
         self.comm = comm
+        self.zc = zc
+        self.ar_algos = ZC_ALGOS if zc else STAGED_ALGOS
         self.L = MPI.lib()
         self.r = MPI.Comm_rank(comm)
         self.n = MPI.Comm_size(comm)
@@ -138,7 +152,7 @@ class Runner:
             ins = typed(arr[c["id"] + ".in"], npdt)
             outs = typed(arr[c["id"] + ".out"], npdt)
             coll = c["coll"]
-            algos = AR_ALGOS if coll in ("allreduce", "reduce") else ("auto",)
+            algos = self.ar_algos if coll in ("allreduce", "reduce") else ("auto",)
             for algo in algos:
                 self.knob("ALGO", algo)
                 for inplace in (False, True):
@@ -248,7 +262,7 @@ class Runner:
         n, r = self.n, self.r
         for i, (dtname, opname, count) in enumerate(sizes):
             ins = make(dtname, opname, n, count, 1000 + i, edge=opname in ("MAX", "MIN"))
-            for algo in AR_ALGOS:
+            for algo in self.ar_algos:
                 self.knob("ALGO", algo)
                 got = self.run("allreduce", ins, dtname, opname, count)
                 self.check(same_bits(got, M.allreduce(ins, dtname, opname)[r], dtname == "BFLOAT16"), ("oracle-allreduce", dtname, opname, count, algo))
@@ -338,7 +352,7 @@ class Runner:
         L.mpigx_comm_set_blocking(cv, 1)
         for k, (ins, count, s, d) in enumerate(burst):
             self.check(same_bits(host(d, np.float32), M.allreduce(ins, "FLOAT", "SUM")[r]), ("ll-burst", k, count))
-        if os.environ.get("MPIGX_ZC_MIN"):
+        if self.zc:
             # LL launches (12 KB IN_PLACE Scans, below a 16 KiB zero-copy
             # threshold) back to back with push two-shots (20 KB Allreduces,
             # above it), whose remote stores into the peers' arenas come before
@@ -485,7 +499,7 @@ class Runner:
         for i, (dtname, opname, count) in enumerate((("FLOAT", "SUM", 5000), ("DOUBLE", "SUM", 70001),
                                                     ("FLOAT", "MAX", 3000), ("BFLOAT16", "SUM", 9999))):
             ins = make(dtname, opname, self.n, count, 500 + i, edge=opname == "MAX")
-            for algo in AR_ALGOS:
+            for algo in self.ar_algos:
                 self.knob("ALGO", algo)
                 got = self.run("allreduce", ins, dtname, opname, count)
                 self.check(same_bits(got, M.fold_linear(ins, dtname, opname), dtname == "BFLOAT16"), ("linear", dtname, opname, algo))
@@ -503,30 +517,34 @@ class Runner:
         self.check(L.mpigx_allreduce(None, None, 0, M.DTYPES["FLOAT"][0], M.OPS["SUM"], cv) == 0, "count0")
 
 
-def main():
-    comm = MPI.Init()
-    R = Runner(comm)
-    phase = os.environ.get("MPIGX_TEST_PHASE", "all")
+def run_pass(name, comm, zc, phase):
+    """Every phase of one pass on comm; returns the pass's summary."""
+    R = Runner(comm, zc)
     if phase != "oracle":  # MPICH-recorded cases exist for n <= 8
         R.golden()
         R.vgolden()
     R.errors()
     R.ll_cases()
-    if not os.environ.get("MPIGX_ZC_MIN"):
+    if not zc:
         R.tune_cases()
     R.oracle_cases([("FLOAT", "SUM", 1_000_003), ("DOUBLE", "SUM", 65537), ("FLOAT", "MAX", 100_001),
                     ("INT32_T", "BAND", 262_147), ("INT64_T", "MAX", 50_000), ("BFLOAT16", "SUM", 40_000),
                     ("C_FLOAT_COMPLEX", "PROD", 3333), ("UINT8_T", "BXOR", 100_000)])
     R.linear_order()
-    zc = bool(os.environ.get("MPIGX_ZC_MIN"))
     if zc:
         R.ring_cases()
         R.unaligned_cases()
     if phase == "all":
         # rounds: a communicator whose staging arena is 1 MiB forces multi-round launches
+        stage = os.environ.get("MPIGX_STAGING_BYTES")
         os.environ["MPIGX_STAGING_BYTES"] = str(1 << 20)
         c2 = MPI.Comm_dup(comm)
-        R2 = Runner(c2)
+        if stage is None:  # the next pass's communicator gets the launch's arena again
+            del os.environ["MPIGX_STAGING_BYTES"]
+        else:
+            os.environ["MPIGX_STAGING_BYTES"] = stage
+        assert MPI.get_knob(c2, "STAGING_BYTES") == 1 << 20
+        R2 = Runner(c2, zc)
         R2.oracle_cases([("FLOAT", "SUM", 700_001), ("DOUBLE", "MIN", 300_001)])
         if zc:
             R2.ring_cases(nchs=(1, 2))
@@ -535,10 +553,38 @@ def main():
         R.ran += R2.ran
     MPI.Barrier(comm)
     pm = list(MPI.peer_memory(comm))  # signalling protocol per peer pair (rw_mask, same_device)
+    summary = {"pass": name, "rank": R.r, "n": R.n, "peer_mem": pm, "checks": R.ran,
+               "failures": [str(f) for f in R.fail[:20]], "nfail": len(R.fail)}
+    if zc:  # launches on an agreed zero-copy view: buffer exchanges, and hits on an earlier exchange's view
+        hits, exch = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+        assert R.L.mpigx_comm_zc_stats(comm.val, ctypes.byref(hits), ctypes.byref(exch)) == 0
+        summary.update(zc_exchanges=exch.value, zc_hits=hits.value)
+    return summary
+
+
+def main():
+    world = MPI.Init()
+    phase = os.environ.get("MPIGX_TEST_PHASE", "all")
+    world_zc = bool(os.environ.get("MPIGX_ZC_MIN"))
+    passes = os.environ.get("GOLDEN_PASSES", "zc" if world_zc else "staged").split(",")
+    assert passes and set(passes) <= {"staged", "zc"} and len(set(passes)) == len(passes), passes
+    summaries = []
+    for name in passes:
+        zc = name == "zc"
+        comm = world
+        if zc != world_zc:
+            assert zc, "a staged pass needs a launch without MPIGX_ZC_MIN"
+            os.environ.update(ZC_ENV)  # every rank, before its part of the collective Comm_dup
+            comm = MPI.Comm_dup(world)
+            assert MPI.get_knob(comm, "ZC_MIN") == 1 and MPI.get_knob(comm, "ZC_REQUIRE") == 1
+            assert MPI.get_knob(comm, "STAGING_BYTES") == MPI.get_knob(world, "STAGING_BYTES")
+        summaries.append(run_pass(name, comm, zc, phase))
+        if comm is not world:
+            MPI.free(comm)
     MPI.Finalize()
-    print(json.dumps({"rank": R.r, "n": R.n, "peer_mem": pm, "checks": R.ran, "failures": [str(f) for f in R.fail[:20]],
-                      "nfail": len(R.fail)}), flush=True)
-    sys.exit(1 if R.fail else 0)
+    for s in summaries:
+        print(json.dumps(s), flush=True)
+    sys.exit(1 if any(s["nfail"] for s in summaries) else 0)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,14 @@ staging and error classes (tests/spmd/golden_worker.py).
 On the 1-GPU test box all ranks share cuda:0 and talk through hipIpc
 exactly as they do across GPUs (peer-mapped HBM, uncached signal arrays);
 grids are capped (MPIGX_MAX_BLOCKS) so every rank's blocks are co-resident.
+
+Process start is a large part of every launch, so a world size is launched
+once, on demand, with the passes it needs (GOLDEN_PASSES): the staged pass on
+COMM_WORLD, and where the zero-copy test has that size, the zero-copy pass
+after it in the same processes, on a communicator created with
+MPIGX_ZC_MIN=1 MPIGX_ZC_REQUIRE=1.  Each test asserts on its own pass.
 """
+import json
 import os
 
 import pytest
@@ -16,45 +23,70 @@ pytestmark = pytest.mark.gpu
 
 ENV = {"MPIGX_DEVICE": "0", "MPIGX_INIT_TIMEOUT_MS": "60000", "MPIGX_MAX_BLOCKS": "16", "MPIGX_TIMEOUT_MS": "30000",
        "MPIGX_STAGING_BYTES": str(64 << 20)}
+WORKER = os.path.join(ROOT, "tests", "spmd", "golden_worker.py")
+
+STAGED_NS = [2, 3, 4, 5, 6, 7, 8]
+ZC_NS = [2, 3, 5, 7, 8]
+_LAUNCHED = {}
 
 
-@pytest.mark.parametrize("n", [2, 3, 4, 5, 6, 8])
-def test_golden_collectives(n):
-    """(~36 s) Every MPICH-recorded golden collective case (tests/golden/mpich_golden.npz) reproduced bit for bit on device at n = 2..8."""
-    rcs, outs = launch(os.path.join(ROOT, "tests", "spmd", "golden_worker.py"), n, timeout=900, extra_env=ENV)
+def _launch(n, passes, **extra):
+    """(exit codes, per-rank output tails, {pass name: [summary per rank]})."""
+    rcs, outs = launch(WORKER, n, timeout=900, extra_env=dict(ENV, GOLDEN_PASSES=",".join(passes), **extra))
     msg = "\n".join(f"--- rank {r} rc={rc}\n{o[-3000:]}" for r, (rc, o) in enumerate(zip(rcs, outs)))
-    assert all(rc == 0 for rc in rcs), msg
-    summ = _summaries(outs)
-    assert len(summ) == n and all(x["nfail"] == 0 and x["checks"] > 200 for x in summ), summ
-    print(summ[0])
-
-
-@pytest.mark.parametrize("n", [2, 3, 5, 8])
-def test_golden_collectives_zero_copy(n):
-    """(~28 s) Every Allreduce through the zero-copy paths (pull: peers read the user
-    buffers through cached hipIpc registrations; push: ranks write into the
-    peers' arenas and recvbufs); MPIGX_ZC_MIN=1 forces them at every size."""
-    env = dict(ENV, MPIGX_ZC_MIN="1", MPIGX_ZC_REQUIRE="1")
-    rcs, outs = launch(os.path.join(ROOT, "tests", "spmd", "golden_worker.py"), n, timeout=900, extra_env=env)
-    msg = "\n".join(f"--- rank {r} rc={rc}\n{o[-3000:]}" for r, (rc, o) in enumerate(zip(rcs, outs)))
-    assert all(rc == 0 for rc in rcs), msg
-    summ = _summaries(outs)
-    assert len(summ) == n and all(x["nfail"] == 0 and x["checks"] > 200 for x in summ), summ
-
-
-def _summaries(outs):
-    import json
-    res = []
+    summ = {p: [] for p in passes}
     for o in outs:
         for line in o.splitlines():
             if line.startswith("{") and '"checks"' in line:
-                res.append(json.loads(line))
-    return res
+                x = json.loads(line)
+                summ[x["pass"]].append(x)
+    return rcs, msg, summ
+
+
+def _golden(n):
+    """The one launch of world size n, made by whichever test asks first."""
+    if n not in _LAUNCHED:
+        _LAUNCHED[n] = _launch(n, ("staged", "zc") if n in ZC_NS else ("staged",))
+    return _LAUNCHED[n]
+
+
+def _check_pass(rcs, msg, summ, n, min_checks):
+    assert all(rc == 0 for rc in rcs), msg
+    assert len(summ) == n and all(x["nfail"] == 0 and x["checks"] > min_checks for x in summ), summ
+    print(json.dumps({"n": n, "pass": summ[0]["pass"], "checks": [x["checks"] for x in summ]}))
+
+
+def _check_zero_copy(summ):
+    # MPIGX_ZC_REQUIRE turns a fall-back to staging into an error; the counter shows the zero-copy launches
+    assert all(x["zc_exchanges"] > 0 for x in summ), summ
+    print(json.dumps({"zc_exchanges": [x["zc_exchanges"] for x in summ], "zc_hits": [x["zc_hits"] for x in summ]}))
+
+
+@pytest.mark.parametrize("n", STAGED_NS)
+def test_golden_collectives(n):
+    """(~37 s) Every MPICH-recorded golden collective case (tests/golden/mpich_golden.npz, mpich_golden_n7_*.npz)
+    reproduced bit for bit on device at n = 2..8; n = 7 is the one size here with three pre-step partners
+    (rem 3 at pof2 4).  The seven launches, zero-copy passes included, measured 65.5 s together; this note
+    and test_golden_collectives_zero_copy's share them by pass."""
+    rcs, msg, summ = _golden(n)
+    _check_pass(rcs, msg, summ["staged"], n, 200)
+
+
+@pytest.mark.parametrize("n", ZC_NS)
+def test_golden_collectives_zero_copy(n):
+    """(~29 s) Every Allreduce through the zero-copy paths (pull: peers read the user
+    buffers through cached hipIpc registrations; push: ranks write into the
+    peers' arenas and recvbufs); MPIGX_ZC_MIN=1 forces them at every size.
+    n = 7: the ring on a prime rank count (strides 1, 6, 2, 5), the push Reduce
+    with six chunk owners, every partition cut in seven."""
+    rcs, msg, summ = _golden(n)
+    _check_pass(rcs, msg, summ["zc"], n, 200)
+    _check_zero_copy(summ["zc"])
 
 
 @pytest.mark.parametrize("n", [9, 10])
 def test_oracle_collectives_many_ranks(n):
-    """(~31 s) n = 9..15: pof2 = 8 with pre-step partners and n-1 > 8 peers to gather
+    """(~23 s) n = 9..15: pof2 = 8 with pre-step partners and n-1 > 8 peers to gather
     from (NMAX 16 kernels), staged and zero-copy paths, vs the oracle (MPICH
     recorded fixtures exist for n <= 8 only).  More than 10 rank processes on
     ONE GPU do not all get hardware queues at once (13 ranks: some ranks'
@@ -62,11 +94,7 @@ def test_oracle_collectives_many_ranks(n):
     timeout), so pre-step counts rem > 4 (n >= 13) are covered by the local
     fold (test_local_gpu.py test_rank_counts, n = 13, 15), which runs the same
     fold code."""
-    for extra in ({}, {"MPIGX_ZC_MIN": "1", "MPIGX_ZC_REQUIRE": "1"}):
-        env = dict(ENV, MPIGX_TEST_PHASE="oracle", MPIGX_MAX_BLOCKS="8", **extra)
-        rcs, outs = launch(os.path.join(ROOT, "tests", "spmd", "golden_worker.py"), n, timeout=900, extra_env=env)
-        msg = "\n".join(f"--- rank {r} rc={rc}\n{o[-3000:]}" for r, (rc, o) in enumerate(zip(rcs, outs)))
-        assert all(rc == 0 for rc in rcs), msg
-        summ = _summaries(outs)
-        assert len(summ) == n and all(x["nfail"] == 0 and x["checks"] > 50 for x in summ), summ
-
+    rcs, msg, summ = _launch(n, ("staged", "zc"), MPIGX_TEST_PHASE="oracle", MPIGX_MAX_BLOCKS="8")
+    for p in ("staged", "zc"):
+        _check_pass(rcs, msg, summ[p], n, 50)
+    _check_zero_copy(summ["zc"])

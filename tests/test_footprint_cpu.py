@@ -9,7 +9,7 @@ import pytest
 import footprint as F
 from oracle import mpich_model as M
 
-NS = (3, 5, 8)
+NS = (3, 5, 7, 8)
 
 
 def _buf(readonly=False, off=12):

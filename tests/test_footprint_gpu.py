@@ -70,9 +70,9 @@ def test_small_arena_round_boundaries():
 
 
 @pytest.mark.slow
-@pytest.mark.parametrize("n", [2, 6])
+@pytest.mark.parametrize("n", [2, 6, 7])
 def test_collectives_footprint_more_sizes(n):
-    """(~8 s) The table at n = 2 (NMAX 2) and n = 6 (rem 2)."""
+    """(~13 s) The table at n = 2 (NMAX 2), n = 6 (rem 2) and n = 7 (rem 3, every partition cut in seven)."""
     _main(n)
 
 

@@ -1,17 +1,18 @@
 """Pins the CPU oracle (oracle/mpich_model.py) to MPICH 3.3.2 itself.
 
-Every case in tests/golden/mpich_golden.npz was recorded by
+Every case in tests/golden/mpich_golden.npz and mpich_golden_n7_*.npz was recorded by
 tests/golden/gen_mpich_golden.c calling MPICH 3.3.2 with the argument shapes of
 MPI.jl's ccall sites (src/collective.jl:34,:304,:498,:615,:698,:765,:839) at
 n = 1..8 ranks; the oracle must reproduce every rank's output bit for bit
 (NaN payloads excepted).
 """
 import collections
+import os
 
 import numpy as np
 import pytest
 
-from golden_io import load, op_type_matrix, same_bits, typed
+from golden_io import golden_files, load, op_type_matrix, same_bits, typed
 from oracle import mpich_model as M
 
 CASES, ARR = load()
@@ -115,9 +116,20 @@ def test_fixture_coverage():
     colls = {c["coll"] for c in CASES}
     assert colls == {"reduce_local", "allreduce", "reduce", "scan", "exscan", "bcast", "allgather", "alltoall",
                      *VCOLLS}
-    assert {c["n"] for c in CASES if c["coll"] == "allreduce"} == {2, 3, 4, 5, 6, 8}
+    assert {c["n"] for c in CASES if c["coll"] == "allreduce"} == {2, 3, 4, 5, 6, 7, 8}
+    assert len({c["id"] for c in CASES}) == len(CASES) and sorted(ARR.files) == sorted(
+        f"{c['id']}.{tag}" for c in CASES for tag in ("in", "out"))
     # the Rabenseifner regime (> 2048 B) is exercised for f32 and f64
     assert any(c["count"] * 4 > 2048 and c["dtype"] == "FLOAT" and c["coll"] == "allreduce" for c in CASES)
+
+
+def test_later_fixture_files_fit_the_repository():
+    """The files added after mpich_golden.npz (n = 7, cut into parts) each stay
+    under the repository's limit of 1 MiB per committed file."""
+    later = golden_files()[1:]
+    assert len(later) >= 2
+    for path in later:
+        assert os.path.getsize(path) < (1 << 20), path
 
 
 def test_bf16_rounding_definition():
@@ -171,7 +183,7 @@ def _ring_step_simulation(inputs, dtname, opname, nch, round_elems):
     return recv
 
 
-@pytest.mark.parametrize("n", [2, 3, 5, 8])
+@pytest.mark.parametrize("n", [2, 3, 5, 7, 8])
 def test_ring_oracle_matches_step_simulation(n):
     """oracle fold_ring (the association the ring kernel is checked against on
     the GPU) equals the ring schedule simulated step by step, on every rank;

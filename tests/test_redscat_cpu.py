@@ -32,11 +32,11 @@ def _nan_blind_equal(a, b):
 
 def test_fixture_covers_the_cases(golden):
     cases, arrays = golden
-    assert sorted({c["n"] for c in cases}) == [1, 2, 3, 4, 5, 6, 8]
+    assert sorted({c["n"] for c in cases}) == [1, 2, 3, 4, 5, 6, 7, 8]
     assert sorted(arrays) == sorted(c["id"] for c in cases)
     for name, _ in R.GOLDEN_FILES:
         assert os.path.getsize(os.path.join(HERE, name)) < (1 << 20), name
-    by_n = {n: [c for c in cases if c["n"] == n] for n in (1, 2, 3, 4, 5, 6, 8)}
+    by_n = {n: [c for c in cases if c["n"] == n] for n in (1, 2, 3, 4, 5, 6, 7, 8)}
     for n, cs in by_n.items():
         assert {c["count"] for c in cs if not c["spans"]} == {1, 3, 1024}
         assert any(c["v"] and 0 in R.counts_of(c, n) for c in cs) or n == 1

@@ -33,11 +33,11 @@ def _run(n, phase, min_checks, **extra):
     return summ
 
 
-@pytest.mark.parametrize("n", [2, 3, 5, 6, 8])
+@pytest.mark.parametrize("n", [2, 3, 5, 6, 7, 8])
 def test_fixtures_staged_and_zero_copy(n):
-    """(~19 s) Every MPICH fixture case at this n on the default (staged) path, then again through
+    """(~25 s) Every MPICH fixture case at this n on the default (staged) path, then again through
     the dedicated zero-copy kernel: NMAX 2 / 4 / 8, full and pre-step shapes (rem 1 at n = 3 and 5,
-    rem 2 at n = 6), odd counts (misaligned blocks), a zero-count rank, both schedules across the
+    rem 2 at n = 6, rem 3 at n = 7), odd counts (misaligned blocks), a zero-count rank, both schedules across the
     512 KiB switch, and the in-place barrier rule."""
     summ = _run(n, "golden", 200, RS_ZC="1")
     assert all(x["zc_exchanges"] > 0 for x in summ), summ

@@ -3471,276 +3471,245 @@ int mpigx_alltoall(const void* sendbuf, int sendcount, int sendtype, void* recvb
 // ---------------------------------------------------------------------------
 // v-collectives and rooted variants (collective.jl:90-578)
 // ---------------------------------------------------------------------------
-// Element size for the v-collectives' byte path: predefined types and
-// contiguous derived types (displacements are in extents, equal to sizes only
-// then).  A call with any other committed type on a side that is read takes
-// the typed path below (needs_pack, *_typed) and never comes here.
-static int vsize(int dtype, int* out) {
-  rt::TypeDesc d;
-  if (rt::type_info(dtype, &d) || !d.contig || d.size > 0x7fffffff) return MPIGX_ERR_TYPE;
-  *out = (int)d.size;
-  return MPIGX_SUCCESS;
-}
-
-static int type_bytes(int dtype, long long count, long long* out) {
-  int sz;
-  if (vsize(dtype, &sz)) return MPIGX_ERR_TYPE;
-  if (count < 0) return MPIGX_ERR_COUNT;
-  *out = count * sz;
-  return MPIGX_SUCCESS;
-}
-
-// A committed derived type that is not `count * size` contiguous bytes: the
-// v-collectives send it through the typed path.
-static bool needs_pack(int dtype) {
-  rt::TypeDesc d;
-  return !rt::type_info(dtype, &d) && d.derived && !d.contig;
-}
-
-// One side of a v-collective in any committed datatype.  Counts and
-// displacements are in extents: instance j of block p lies at
-// user + (dsp[p] + j) * extent.  A contiguous type is addressed in place
-// (block p = len[p] bytes at off[p] = dsp[p] * size).  Any other type goes
-// through a pooled temporary in which block p's packed bytes start at the
-// 16-B-aligned prefix off[p], so that the byte-moving vexchange moves them
-// unchanged, and ONE seg_pack_kernel launch packs (before the exchange) or
-// unpacks (after it) every block.
-struct VSide {
-  mpigx_comm* c = nullptr;
-  rt::TypeDesc d{};
-  int type = 0, nseg = 0;
+// One side (send or receive) of Gather(v) / Scatter(v) / Allgatherv /
+// Alltoallv / Alltoallw: nseg blocks, block p = cnt[p] instances of type[p] at
+// the caller's displacement dsp[p].
+//   uniform side    one datatype (type[0]), displacements in extents; packed
+//                   by ONE seg_pack_kernel launch (rt::type_pack_seg)
+//   per-block side  Alltoallw: a datatype per block, displacements in bytes;
+//                   packed by ONE segw_pack_kernel launch (rt::type_pack_segw)
+// A side whose non-empty blocks are all predefined or contiguous is addressed
+// in place (block p = len[p] bytes at off[p] from the caller's pointer): no
+// temporary, no launch.  Any other side goes through a pooled temporary in
+// which block p's packed bytes start at the 16-B-aligned prefix off[p], so
+// that the byte-moving vexchange moves them unchanged.  A side that was never
+// filled (a non-root's, the send side under IN_PLACE) has no blocks and takes
+// no part.  The temporary returns to the pool when the side leaves scope:
+// after the call's last finish(), on every return path.
+struct Side {
+  mpigx_comm* c = nullptr;  // set once filled
+  int nseg = 0;
+  bool uniform = true;
+  bool must = false;  // a root's buffer of a rooted call: refused when null even if every count is 0
   bool pack = false;
-  char* user = nullptr;  // the typed buffer
+  char* user = nullptr;  // the caller's buffer
   char* buf = nullptr;   // what vexchange addresses: user, or the temporary
   char* tmp = nullptr;
+  long long unit = 1;   // bytes per displacement step of an in-place block
+  long long total = 0;  // packed bytes, each block rounded up to 16
+  int type[kMaxRanks] = {};
   long long cnt[kMaxRanks] = {}, dsp[kMaxRanks] = {}, off[kMaxRanks] = {}, len[kMaxRanks] = {};
-  ~VSide() {
+  ~Side() {
     if (tmp) tmp_put(c, tmp, 0);
   }
 };
 
-// counts == NULL: one block of count1 instances at the pointer.
-static int vside_init(mpigx_comm* c, VSide* v, int type, const void* user, int nseg, const int* counts,
-                      const int* displs, int count1) {
-  if (rt::type_info(type, &v->d)) return MPIGX_ERR_TYPE;
+// Fill from the caller's arrays: a per-block side with types[], a uniform
+// side of `type` without.
+static void side_blocks(Side* v, mpigx_comm* c, const void* user, int nseg, const int* counts, const int* displs,
+                        const int* types, int type) {
   v->c = c;
-  v->type = type;
-  v->nseg = nseg;
   v->user = (char*)user;
-  v->pack = v->d.derived && !v->d.contig;
-  long long total = 0;
+  v->nseg = nseg;
+  v->uniform = !types;
   for (int p = 0; p < nseg; ++p) {
-    v->cnt[p] = counts ? counts[p] : count1;
+    v->cnt[p] = counts[p];
+    v->dsp[p] = displs[p];
+    v->type[p] = types ? types[p] : type;
+  }
+}
+
+// Fill from one count: nseg equal blocks, block p at p * count (nseg = 1: one
+// block at the pointer).
+static void side_equal(Side* v, mpigx_comm* c, const void* user, int nseg, int count, int type) {
+  v->c = c;
+  v->user = (char*)user;
+  v->nseg = nseg;
+  for (int p = 0; p < nseg; ++p) {
+    v->cnt[p] = count;
+    v->dsp[p] = (long long)p * count;
+    v->type[p] = type;
+  }
+}
+
+// Argument checks of one side; nothing is allocated.  Counts first, then the
+// types (every slot of a per-block side, even where its count is 0), then the
+// buffer.  An in-place uniform side multiplies int displacements by the size,
+// so a contiguous type past 2^31 - 1 bytes is refused.
+static int side_check(Side* v) {
+  for (int p = 0; p < v->nseg; ++p)
     if (v->cnt[p] < 0) return MPIGX_ERR_COUNT;
-    v->dsp[p] = counts ? displs[p] : 0;
-    v->len[p] = v->cnt[p] * v->d.size;
-    v->off[p] = v->pack ? total : v->dsp[p] * v->d.size;
-    total += (v->len[p] + 15) & ~15ll;
+  rt::TypeDesc d{};
+  for (int p = 0; p < v->nseg; ++p) {
+    if (p == 0 || !v->uniform) {
+      if (rt::type_info(v->type[p], &d)) return MPIGX_ERR_TYPE;
+      if (v->uniform && d.contig && d.size > 0x7fffffff) return MPIGX_ERR_TYPE;
+    }
+    v->len[p] = v->cnt[p] * d.size;
+    if (v->len[p] && !d.contig) v->pack = true;
+    v->total += (v->len[p] + 15) & ~15ll;
+  }
+  if (v->uniform) v->unit = d.size;
+  if (!v->user && (v->must || v->total)) return MPIGX_ERR_BUFFER;
+  return MPIGX_SUCCESS;
+}
+
+// After both sides' checks: the blocks' offsets, and the temporary of a
+// packed side.
+static int side_place(Side* v) {
+  long long at = 0;
+  for (int p = 0; p < v->nseg; ++p) {
+    v->off[p] = v->pack ? at : v->dsp[p] * v->unit;
+    at += (v->len[p] + 15) & ~15ll;
   }
   v->buf = v->user;
-  if (total && !user) return MPIGX_ERR_BUFFER;
   if (v->pack) {
-    if (!(v->tmp = tmp_get(c, total > 16 ? total : 16))) return MPIGX_ERR_NO_MEM;
+    if (!(v->tmp = tmp_get(v->c, v->total > 16 ? v->total : 16))) return MPIGX_ERR_NO_MEM;
     v->buf = v->tmp;
   }
   return MPIGX_SUCCESS;
 }
 
-// Pack (unpack = 0) or unpack every block of a packed side on the comm's
-// stream; block `skip` (if >= 0) is left alone.
-static int vside_move(VSide* v, int unpack, int skip = -1) {
+// Pack (unpack = 0) or unpack the blocks of a packed side in one launch on
+// the comm's stream: block `only` alone if >= 0, every block but `skip`
+// otherwise.
+static int side_move(Side* v, int unpack, int only, int skip) {
   if (!v->pack) return MPIGX_SUCCESS;
   long long cnt[kMaxRanks];
-  for (int p = 0; p < v->nseg; ++p) cnt[p] = p == skip ? 0 : v->cnt[p];
-  const int rc = rt::type_pack_seg(v->type, v->user, v->nseg, cnt, v->dsp, v->off, v->tmp, unpack, v->c->device,
-                                   v->c->stream);
+  for (int p = 0; p < v->nseg; ++p) cnt[p] = (p == skip || (only >= 0 && p != only)) ? 0 : v->cnt[p];
+  int rc;
+  if (v->uniform) {
+    rc = rt::type_pack_seg(v->type[0], v->user, v->nseg, cnt, v->dsp, v->off, v->tmp, unpack, v->c->device,
+                           v->c->stream);
+  } else {
+    rt::SegWSpec segs[kMaxRanks];
+    for (int p = 0; p < v->nseg; ++p) segs[p] = {v->type[p], cnt[p], v->dsp[p], v->off[p]};
+    rc = rt::type_pack_segw(v->user, v->nseg, segs, v->tmp, unpack, v->c->device, v->c->stream, nullptr);
+  }
   if (!rc) v->c->unflagged = true;  // the final finish() drains the stream
   return rc;
 }
 
-static int gatherv_typed(const void* send, int scount, int stype, void* recv, const int* rcounts, const int* displs,
-                         int rtype, int root, mpigx_comm_t c) {
-  int rc = check_comm(c);
-  if (rc) return rc;
-  const int n = c->n, r = c->rank;
-  if (root < 0 || root >= n) return MPIGX_ERR_ROOT;
-  const bool isroot = r == root, inplace = send == MPIGX_IN_PLACE;
-  if (inplace && !isroot) return MPIGX_ERR_BUFFER;
-  VSide S, R;
-  VSpec s;
-  if (isroot) {
-    if (!recv) return MPIGX_ERR_BUFFER;
-    if ((rc = vside_init(c, &R, rtype, recv, n, rcounts, displs, 0))) return rc;
-    for (int p = 0; p < n; ++p) {
-      s.p_len[p] = R.len[p];
-      s.p_slot[p] = 0;
-      s.p_dst[p] = R.off[p];
+// The three exchange shapes.  r = this rank; under IN_PLACE the own block
+// stays where it is and its length is zeroed.
+//
+// Gather: every rank copies ONE block into its slot 0, and a root (a rank
+// whose R is filled) pulls slot 0 of rank p into block p of R.  Allgatherv
+// (`all`) is this shape with every rank a root; its IN_PLACE contribution is
+// block r of R, which the peers still pull.
+static void spec_gather(VSpec* s, const Side* S, const Side* R, int r, bool inplace, bool all) {
+  if (R->c) {
+    for (int p = 0; p < R->nseg; ++p) {
+      s->p_len[p] = R->len[p];
+      s->p_slot[p] = 0;
+      s->p_dst[p] = R->off[p];
     }
-    if (inplace) s.p_len[r] = 0;
+    if (inplace) s->p_len[r] = 0;
+    s->recv = R->buf;
   }
-  if (!inplace) {
-    if ((rc = vside_init(c, &S, stype, send, 1, nullptr, nullptr, scount))) return rc;
-    s.ncopy = 1;
-    s.c_slot[0] = 0;
-    s.c_src[0] = S.off[0];
-    s.c_len[0] = S.len[0];
+  if (!inplace || all) {
+    const Side* O = inplace ? R : S;
+    const int b = inplace ? r : 0;
+    s->ncopy = 1;
+    s->c_slot[0] = 0;
+    s->c_src[0] = O->off[b];
+    s->c_len[0] = O->len[b];
+    s->send = O->buf;
   }
-  s.send = S.buf;
-  s.recv = R.buf;
-  rc = vside_move(&S, 0);
+}
+
+// Scatter: the root copies block q of S into slot q; every rank whose R is
+// filled pulls the root's slot r into its one block.
+static void spec_scatter(VSpec* s, const Side* S, const Side* R, int r, int root, bool inplace) {
+  if (S->c) {
+    s->ncopy = S->nseg;
+    for (int q = 0; q < S->nseg; ++q) {
+      s->c_slot[q] = q;
+      s->c_src[q] = S->off[q];
+      s->c_len[q] = S->len[q];
+    }
+    if (inplace) s->c_len[r] = 0;
+    s->send = S->buf;
+  }
+  if (R->c) {
+    s->p_len[root] = R->len[0];
+    s->p_slot[root] = r;
+    s->p_dst[root] = R->off[0];
+    s->recv = R->buf;
+  }
+}
+
+// All-to-all: block q of S goes into slot q, slot r of rank q comes into
+// block q of R.  MPI-2.2 IN_PLACE: the send layout is the receive layout.
+static void spec_alltoall(VSpec* s, const Side* S, const Side* R, int r, bool inplace) {
+  const Side* O = inplace ? R : S;
+  s->ncopy = R->nseg;
+  for (int q = 0; q < R->nseg; ++q) {
+    s->c_slot[q] = q;
+    s->c_src[q] = O->off[q];
+    s->c_len[q] = O->len[q];
+    s->p_len[q] = R->len[q];
+    s->p_slot[q] = r;
+    s->p_dst[q] = R->off[q];
+  }
+  s->send = O->buf;
+  s->recv = R->buf;
+}
+
+enum VShape { kGatherShape, kAllgatherShape, kScatterShape, kAlltoallShape };
+
+// Runs one v-collective over its filled sides: every check of both sides
+// (receive side first), then the offsets and temporaries, pack, vexchange,
+// unpack, finish.  Blocks moved under IN_PLACE: Allgatherv packs block r only
+// and Scatterv all but r; Gatherv and Allgatherv unpack all but r; Alltoallv /
+// Alltoallw pack and unpack the receive side whole.  vexchange ends in
+// finish(), so only a launched unpack needs another.
+static int side_exchange(mpigx_comm* c, VShape shape, Side* S, Side* R, int root, bool inplace) {
+  const int r = c->rank, own = inplace ? r : -1;
+  int rc;
+  if ((rc = side_check(R)) || (rc = side_check(S))) return rc;
+  if ((rc = side_place(R)) || (rc = side_place(S))) return rc;
+  VSpec s;
+  if (shape == kScatterShape) spec_scatter(&s, S, R, r, root, inplace);
+  else if (shape == kAlltoallShape) spec_alltoall(&s, S, R, r, inplace);
+  else spec_gather(&s, S, R, r, inplace, shape == kAllgatherShape);
+  Side* O = inplace && (shape == kAllgatherShape || shape == kAlltoallShape) ? R : S;
+  rc = side_move(O, 0, shape == kAllgatherShape ? own : -1, shape == kScatterShape ? own : -1);
   if (!rc) rc = vexchange(c, s);
-  if (!rc) rc = vside_move(&R, 1, inplace ? r : -1);
-  if (!rc) rc = finish(c);
+  if (!rc && R->pack) {
+    rc = side_move(R, 1, -1, shape == kAlltoallShape ? -1 : own);
+    if (!rc) rc = finish(c);
+  }
   return rc;
 }
 
-static int scatterv_typed(const void* send, const int* scounts, const int* displs, int stype, void* recv, int rcount,
-                          int rtype, int root, mpigx_comm_t c) {
-  int rc = check_comm(c);
+// Checks every rooted call starts with: communicator, root, IN_PLACE at a
+// non-root.
+static int check_rooted(mpigx_comm* c, int root, bool inplace) {
+  const int rc = check_comm(c);
   if (rc) return rc;
-  const int n = c->n, r = c->rank;
-  if (root < 0 || root >= n) return MPIGX_ERR_ROOT;
-  const bool isroot = r == root, inplace = recv == MPIGX_IN_PLACE;
-  if (inplace && !isroot) return MPIGX_ERR_BUFFER;
-  VSide S, R;
-  VSpec s;
-  if (isroot) {
-    if (!send) return MPIGX_ERR_BUFFER;
-    if ((rc = vside_init(c, &S, stype, send, n, scounts, displs, 0))) return rc;
-    s.ncopy = n;
-    for (int q = 0; q < n; ++q) {
-      s.c_slot[q] = q;
-      s.c_src[q] = S.off[q];
-      s.c_len[q] = (inplace && q == r) ? 0 : S.len[q];
-    }
-  }
-  if (!inplace) {
-    if ((rc = vside_init(c, &R, rtype, recv, 1, nullptr, nullptr, rcount))) return rc;
-    s.p_len[root] = R.len[0];
-    s.p_slot[root] = r;
-    s.p_dst[root] = R.off[0];
-  }
-  s.send = S.buf;
-  s.recv = R.buf;
-  rc = vside_move(&S, 0, inplace ? r : -1);
-  if (!rc) rc = vexchange(c, s);
-  if (!rc) rc = vside_move(&R, 1);
-  if (!rc) rc = finish(c);
-  return rc;
+  if (root < 0 || root >= c->n) return MPIGX_ERR_ROOT;
+  if (inplace && c->rank != root) return MPIGX_ERR_BUFFER;
+  return MPIGX_SUCCESS;
 }
 
-static int allgatherv_typed(const void* send, int scount, int stype, void* recv, const int* rcounts,
-                            const int* displs, int rtype, mpigx_comm_t c) {
-  int rc = check_comm(c);
-  if (rc) return rc;
-  if (!rcounts || !displs) return MPIGX_ERR_ARG;
-  const int n = c->n, r = c->rank;
+// MPI_Gather / MPI_Gatherv (collective.jl:230-246, 363-382).  rcounts/displs
+// (in recvtype extents) are read at the root only; `v` false => equal blocks
+// of rcount.
+static int gather_sides(const void* send, int scount, int stype, void* recv, int rcount, const int* rcounts,
+                        const int* displs, int rtype, int root, bool v, mpigx_comm_t c) {
   const bool inplace = send == MPIGX_IN_PLACE;
-  VSide S, R;
-  VSpec s;
-  if ((rc = vside_init(c, &R, rtype, recv, n, rcounts, displs, 0))) return rc;
-  for (int p = 0; p < n; ++p) {
-    s.p_len[p] = R.len[p];
-    s.p_slot[p] = 0;
-    s.p_dst[p] = R.off[p];
-  }
-  s.ncopy = 1;
-  s.c_slot[0] = 0;
-  if (inplace) {  // my contribution is block r of the receive side (packed first if the type needs it)
-    long long mine[kMaxRanks] = {};
-    mine[r] = R.cnt[r];
-    if (R.pack) {
-      rc = rt::type_pack_seg(rtype, R.user, n, mine, R.dsp, R.off, R.tmp, 0, c->device, c->stream);
-      if (rc) return rc;
-      c->unflagged = true;
-    }
-    s.send = R.buf;
-    s.c_src[0] = R.off[r];
-    s.c_len[0] = R.len[r];
-    s.p_len[r] = 0;
-  } else {
-    if ((rc = vside_init(c, &S, stype, send, 1, nullptr, nullptr, scount))) return rc;
-    s.send = S.buf;
-    s.c_src[0] = S.off[0];
-    s.c_len[0] = S.len[0];
-    if ((rc = vside_move(&S, 0))) return rc;
-  }
-  s.recv = R.buf;
-  rc = vexchange(c, s);
-  if (!rc) rc = vside_move(&R, 1, inplace ? r : -1);
-  if (!rc) rc = finish(c);
-  return rc;
-}
-
-static int alltoallv_typed(const void* send, const int* scounts, const int* sdispls, int stype, void* recv,
-                           const int* rcounts, const int* rdispls, int rtype, mpigx_comm_t c) {
-  int rc = check_comm(c);
+  const int rc = check_rooted(c, root, inplace);
   if (rc) return rc;
-  if (!rcounts || !rdispls) return MPIGX_ERR_ARG;
-  const int n = c->n, r = c->rank;
-  const bool inplace = send == MPIGX_IN_PLACE;
-  if (!inplace && (!scounts || !sdispls)) return MPIGX_ERR_ARG;
-  VSide S, R;
-  VSpec s;
-  if ((rc = vside_init(c, &R, rtype, recv, n, rcounts, rdispls, 0))) return rc;
-  if (!inplace && (rc = vside_init(c, &S, stype, send, n, scounts, sdispls, 0))) return rc;
-  // MPI-2.2 IN_PLACE: the send layout is the receive layout
-  VSide& O = inplace ? R : S;
-  s.ncopy = n;
-  for (int q = 0; q < n; ++q) {
-    s.c_slot[q] = q;
-    s.c_src[q] = O.off[q];
-    s.c_len[q] = O.len[q];
-    s.p_len[q] = R.len[q];
-    s.p_slot[q] = r;
-    s.p_dst[q] = R.off[q];
+  Side S, R;
+  if (c->rank == root) {
+    if (v && (!rcounts || !displs)) return MPIGX_ERR_ARG;
+    if (v) side_blocks(&R, c, recv, c->n, rcounts, displs, nullptr, rtype);
+    else side_equal(&R, c, recv, c->n, rcount, rtype);
+    R.must = true;
   }
-  s.send = O.buf;
-  s.recv = R.buf;
-  rc = vside_move(&O, 0);
-  if (!rc) rc = vexchange(c, s);
-  if (!rc) rc = vside_move(&R, 1);
-  if (!rc) rc = finish(c);
-  return rc;
-}
-
-// MPI_Gather / MPI_Gatherv (collective.jl:230-246, 363-382).  counts/displs
-// (in recvtype elements) are read at the root only; NULL => equal blocks.
-static int gather_common(const void* send, int scount, int stype, void* recv, int rcount, const int* rcounts,
-                         const int* displs, int rtype, int root, mpigx_comm_t c) {
-  int rc = check_comm(c);
-  if (rc) return rc;
-  const int n = c->n, r = c->rank;
-  if (root < 0 || root >= n) return MPIGX_ERR_ROOT;
-  const bool isroot = r == root, inplace = send == MPIGX_IN_PLACE;
-  if (inplace && !isroot) return MPIGX_ERR_BUFFER;
-  VSpec s;
-  int rsz = 0;
-  if (isroot) {
-    if ((rc = vsize(rtype, &rsz))) return rc;
-    if (!recv) return MPIGX_ERR_BUFFER;
-    for (int p = 0; p < n; ++p) {
-      const long long cnt = rcounts ? rcounts[p] : rcount;
-      if (cnt < 0) return MPIGX_ERR_COUNT;
-      const long long dsp = rcounts ? displs[p] : (long long)p * rcount;
-      s.p_len[p] = cnt * rsz;
-      s.p_slot[p] = 0;
-      s.p_dst[p] = dsp * rsz;
-    }
-    if (inplace) s.p_len[r] = 0;
-  }
-  if (!inplace) {
-    long long sb;
-    if ((rc = type_bytes(stype, scount, &sb))) return rc;
-    if (sb && !send) return MPIGX_ERR_BUFFER;
-    s.ncopy = 1;
-    s.c_slot[0] = 0;
-    s.c_src[0] = 0;
-    s.c_len[0] = sb;
-  }
-  s.send = (const char*)send;
-  s.recv = (char*)recv;
-  return vexchange(c, s);
+  if (!inplace) side_equal(&S, c, send, 1, scount, stype);
+  return side_exchange(c, kGatherShape, &S, &R, root, inplace);
 }
 
 int mpigx_gather(const void* sendbuf, int sendcount, int sendtype, void* recvbuf, int recvcount, int recvtype,
@@ -3751,7 +3720,7 @@ int mpigx_gather(const void* sendbuf, int sendcount, int sendtype, void* recvbuf
   if (root < 0 || root >= c->n) return MPIGX_ERR_ROOT;
   const bool isroot = c->rank == root;
   if ((inplace || !derived(sendtype)) && (!isroot || !derived(recvtype)))
-    return gather_common(sendbuf, sendcount, sendtype, recvbuf, recvcount, nullptr, nullptr, recvtype, root, c);
+    return gather_sides(sendbuf, sendcount, sendtype, recvbuf, recvcount, nullptr, nullptr, recvtype, root, false, c);
   // derived types: pack my contribution / receive packed blocks at the root
   rt::TypeDesc sd, rd;
   int sb = 0, rb = 0;
@@ -3774,7 +3743,7 @@ int mpigx_gather(const void* sendbuf, int sendcount, int sendtype, void* recvbuf
                    rtmp + (long long)root * rb, rb, 0);
     dst = rtmp;
   }
-  if (!rc) rc = gather_common(src, inplace ? 0 : sb, MPIGX_BYTE, dst, rb, nullptr, nullptr, MPIGX_BYTE, root, c);
+  if (!rc) rc = gather_sides(src, inplace ? 0 : sb, MPIGX_BYTE, dst, rb, nullptr, nullptr, MPIGX_BYTE, root, false, c);
   if (!rc && rtmp) rc = pack_on(c, recvtype, recvbuf, (long long)n * recvcount, rtmp, (long long)n * rb, 1);
   if (!rc) rc = finish(c);
   if (stmp) tmp_put(c, stmp, 0);
@@ -3783,47 +3752,26 @@ int mpigx_gather(const void* sendbuf, int sendcount, int sendtype, void* recvbuf
 }
 int mpigx_gatherv(const void* sendbuf, int sendcount, int sendtype, void* recvbuf, const int* recvcounts,
                   const int* displs, int recvtype, int root, mpigx_comm_t c) {
-  if (c && c->rank == root && (!recvcounts || !displs)) return MPIGX_ERR_ARG;
-  if (c && ((sendbuf != MPIGX_IN_PLACE && needs_pack(sendtype)) || (c->rank == root && needs_pack(recvtype))))
-    return gatherv_typed(sendbuf, sendcount, sendtype, recvbuf, recvcounts, displs, recvtype, root, c);
-  return gather_common(sendbuf, sendcount, sendtype, recvbuf, 0, recvcounts, displs, recvtype, root, c);
+  return gather_sides(sendbuf, sendcount, sendtype, recvbuf, 0, recvcounts, displs, recvtype, root, true, c);
 }
 
-// MPI_Scatter / MPI_Scatterv (collective.jl:90-106, 156-175).
-static int scatter_common(const void* send, int scount, const int* scounts, const int* displs, int stype, void* recv,
-                          int rcount, int rtype, int root, mpigx_comm_t c) {
-  int rc = check_comm(c);
+// MPI_Scatter / MPI_Scatterv (collective.jl:90-106, 156-175).  scounts/displs
+// (in sendtype extents) are read at the root only; `v` false => equal blocks
+// of scount.
+static int scatter_sides(const void* send, int scount, const int* scounts, const int* displs, int stype, void* recv,
+                         int rcount, int rtype, int root, bool v, mpigx_comm_t c) {
+  const bool inplace = recv == MPIGX_IN_PLACE;
+  const int rc = check_rooted(c, root, inplace);
   if (rc) return rc;
-  const int n = c->n, r = c->rank;
-  if (root < 0 || root >= n) return MPIGX_ERR_ROOT;
-  const bool isroot = r == root, inplace = recv == MPIGX_IN_PLACE;
-  if (inplace && !isroot) return MPIGX_ERR_BUFFER;
-  VSpec s;
-  if (isroot) {
-    int ssz = 0;
-    if ((rc = vsize(stype, &ssz))) return rc;
-    if (!send) return MPIGX_ERR_BUFFER;
-    s.ncopy = n;
-    for (int q = 0; q < n; ++q) {
-      const long long cnt = scounts ? scounts[q] : scount;
-      if (cnt < 0) return MPIGX_ERR_COUNT;
-      const long long dsp = scounts ? displs[q] : (long long)q * scount;
-      s.c_slot[q] = q;
-      s.c_src[q] = dsp * ssz;
-      s.c_len[q] = (inplace && q == r) ? 0 : cnt * ssz;
-    }
+  Side S, R;
+  if (c->rank == root) {
+    if (v && (!scounts || !displs)) return MPIGX_ERR_ARG;
+    if (v) side_blocks(&S, c, send, c->n, scounts, displs, nullptr, stype);
+    else side_equal(&S, c, send, c->n, scount, stype);
+    S.must = true;
   }
-  if (!inplace) {
-    long long rb;
-    if ((rc = type_bytes(rtype, rcount, &rb))) return rc;
-    if (rb && !recv) return MPIGX_ERR_BUFFER;
-    s.p_len[root] = rb;
-    s.p_slot[root] = r;
-    s.p_dst[root] = 0;
-  }
-  s.send = (const char*)send;
-  s.recv = (char*)recv;
-  return vexchange(c, s);
+  if (!inplace) side_equal(&R, c, recv, 1, rcount, rtype);
+  return side_exchange(c, kScatterShape, &S, &R, root, inplace);
 }
 
 int mpigx_scatter(const void* sendbuf, int sendcount, int sendtype, void* recvbuf, int recvcount, int recvtype,
@@ -3834,7 +3782,7 @@ int mpigx_scatter(const void* sendbuf, int sendcount, int sendtype, void* recvbu
   if (root < 0 || root >= c->n) return MPIGX_ERR_ROOT;
   const bool isroot = c->rank == root;
   if ((!isroot || !derived(sendtype)) && (inplace || !derived(recvtype)))
-    return scatter_common(sendbuf, sendcount, nullptr, nullptr, sendtype, recvbuf, recvcount, recvtype, root, c);
+    return scatter_sides(sendbuf, sendcount, nullptr, nullptr, sendtype, recvbuf, recvcount, recvtype, root, false, c);
   rt::TypeDesc sd, rd;
   int sb = 0, rb = 0;
   if (!inplace && (rc = bytes_of(recvtype, recvcount, &rd, &rb))) return rc;
@@ -3853,7 +3801,7 @@ int mpigx_scatter(const void* sendbuf, int sendcount, int sendtype, void* recvbu
     if (!(rtmp = tmp_get(c, rb > 0 ? rb : 1))) rc = MPIGX_ERR_NO_MEM;
     dst = rtmp;
   }
-  if (!rc) rc = scatter_common(src, sb, nullptr, nullptr, MPIGX_BYTE, dst, inplace ? 0 : rb, MPIGX_BYTE, root, c);
+  if (!rc) rc = scatter_sides(src, sb, nullptr, nullptr, MPIGX_BYTE, dst, inplace ? 0 : rb, MPIGX_BYTE, root, false, c);
   if (!rc && rtmp) rc = pack_on(c, recvtype, recvbuf, recvcount, rtmp, rb, 1);
   if (!rc) rc = finish(c);
   if (stmp) tmp_put(c, stmp, 0);
@@ -3862,187 +3810,48 @@ int mpigx_scatter(const void* sendbuf, int sendcount, int sendtype, void* recvbu
 }
 int mpigx_scatterv(const void* sendbuf, const int* sendcounts, const int* displs, int sendtype, void* recvbuf,
                    int recvcount, int recvtype, int root, mpigx_comm_t c) {
-  if (c && c->rank == root && (!sendcounts || !displs)) return MPIGX_ERR_ARG;
-  if (c && ((recvbuf != MPIGX_IN_PLACE && needs_pack(recvtype)) || (c->rank == root && needs_pack(sendtype))))
-    return scatterv_typed(sendbuf, sendcounts, displs, sendtype, recvbuf, recvcount, recvtype, root, c);
-  return scatter_common(sendbuf, 0, sendcounts, displs, sendtype, recvbuf, recvcount, recvtype, root, c);
+  return scatter_sides(sendbuf, 0, sendcounts, displs, sendtype, recvbuf, recvcount, recvtype, root, true, c);
 }
 
 // MPI_Allgatherv (collective.jl:424-437)
 int mpigx_allgatherv(const void* sendbuf, int sendcount, int sendtype, void* recvbuf, const int* recvcounts,
                      const int* displs, int recvtype, mpigx_comm_t c) {
-  if (needs_pack(recvtype) || (sendbuf != MPIGX_IN_PLACE && needs_pack(sendtype)))
-    return allgatherv_typed(sendbuf, sendcount, sendtype, recvbuf, recvcounts, displs, recvtype, c);
-  int rc = check_comm(c);
+  const int rc = check_comm(c);
   if (rc) return rc;
   if (!recvcounts || !displs) return MPIGX_ERR_ARG;
-  const int n = c->n, r = c->rank;
-  int rsz = 0;
-  if ((rc = vsize(recvtype, &rsz))) return rc;
   const bool inplace = sendbuf == MPIGX_IN_PLACE;
-  VSpec s;
-  for (int p = 0; p < n; ++p) {
-    if (recvcounts[p] < 0) return MPIGX_ERR_COUNT;
-    s.p_len[p] = (long long)recvcounts[p] * rsz;
-    s.p_slot[p] = 0;
-    s.p_dst[p] = (long long)displs[p] * rsz;
-  }
-  if (!recvbuf && s.p_len[r]) return MPIGX_ERR_BUFFER;
-  s.ncopy = 1;
-  s.c_slot[0] = 0;
-  if (inplace) {
-    s.send = (const char*)recvbuf;
-    s.c_src[0] = s.p_dst[r];
-    s.c_len[0] = s.p_len[r];
-    s.p_len[r] = 0;
-  } else {
-    long long sb;
-    if ((rc = type_bytes(sendtype, sendcount, &sb))) return rc;
-    if (sb && !sendbuf) return MPIGX_ERR_BUFFER;
-    s.send = (const char*)sendbuf;
-    s.c_src[0] = 0;
-    s.c_len[0] = sb;
-  }
-  s.recv = (char*)recvbuf;
-  return vexchange(c, s);
+  Side S, R;
+  side_blocks(&R, c, recvbuf, c->n, recvcounts, displs, nullptr, recvtype);
+  if (!inplace) side_equal(&S, c, sendbuf, 1, sendcount, sendtype);
+  return side_exchange(c, kAllgatherShape, &S, &R, 0, inplace);
 }
 
-// MPI_Alltoallv (collective.jl:545-559); MPI-2.2 IN_PLACE takes the send
-// layout from recvcounts/rdispls.
+// MPI_Alltoallv (collective.jl:545-559) and MPI_Alltoallw: Alltoallw gives
+// stypes/rtypes, a datatype per peer with byte displacements; Alltoallv gives
+// none, and stype/rtype with displacements in extents.  MPI-2.2 IN_PLACE takes
+// the send layout from the receive arguments.
+static int alltoall_sides(const void* send, const int* scounts, const int* sdispls, const int* stypes, int stype,
+                          void* recv, const int* rcounts, const int* rdispls, const int* rtypes, int rtype, bool w,
+                          mpigx_comm_t c) {
+  const int rc = check_comm(c);
+  if (rc) return rc;
+  const bool inplace = send == MPIGX_IN_PLACE;
+  if (!rcounts || !rdispls || (w && !rtypes)) return MPIGX_ERR_ARG;
+  if (!inplace && (!scounts || !sdispls || (w && !stypes))) return MPIGX_ERR_ARG;
+  Side S, R;
+  side_blocks(&R, c, recv, c->n, rcounts, rdispls, rtypes, rtype);
+  if (!inplace) side_blocks(&S, c, send, c->n, scounts, sdispls, stypes, stype);
+  return side_exchange(c, kAlltoallShape, &S, &R, 0, inplace);
+}
 int mpigx_alltoallv(const void* sendbuf, const int* sendcounts, const int* sdispls, int sendtype, void* recvbuf,
                     const int* recvcounts, const int* rdispls, int recvtype, mpigx_comm_t c) {
-  if (needs_pack(recvtype) || (sendbuf != MPIGX_IN_PLACE && needs_pack(sendtype)))
-    return alltoallv_typed(sendbuf, sendcounts, sdispls, sendtype, recvbuf, recvcounts, rdispls, recvtype, c);
-  int rc = check_comm(c);
-  if (rc) return rc;
-  if (!recvcounts || !rdispls) return MPIGX_ERR_ARG;
-  const int n = c->n, r = c->rank;
-  const bool inplace = sendbuf == MPIGX_IN_PLACE;
-  int rsz = 0, ssz = 0;
-  if ((rc = vsize(recvtype, &rsz))) return rc;
-  if (!inplace) {
-    if (!sendcounts || !sdispls) return MPIGX_ERR_ARG;
-    if ((rc = vsize(sendtype, &ssz))) return rc;
-  }
-  VSpec s;
-  s.ncopy = n;
-  for (int q = 0; q < n; ++q) {
-    const long long sc = inplace ? recvcounts[q] : sendcounts[q];
-    const long long sd = inplace ? rdispls[q] : sdispls[q];
-    if (sc < 0 || recvcounts[q] < 0) return MPIGX_ERR_COUNT;
-    s.c_slot[q] = q;
-    s.c_src[q] = sd * (inplace ? rsz : ssz);
-    s.c_len[q] = sc * (inplace ? rsz : ssz);
-    s.p_len[q] = (long long)recvcounts[q] * rsz;
-    s.p_slot[q] = r;
-    s.p_dst[q] = (long long)rdispls[q] * rsz;
-  }
-  s.send = inplace ? (const char*)recvbuf : (const char*)sendbuf;
-  s.recv = (char*)recvbuf;
-  return vexchange(c, s);
+  return alltoall_sides(sendbuf, sendcounts, sdispls, nullptr, sendtype, recvbuf, recvcounts, rdispls, nullptr,
+                        recvtype, false, c);
 }
-
-// One side of Alltoallw: block q has its own datatype, count and BYTE
-// displacement.  A side whose every non-empty block is predefined or
-// contiguous is addressed in place (block q = len[q] bytes at dsp[q]).  Any
-// other side goes through a pooled temporary in which block q's packed bytes
-// start at the 16-B-aligned prefix off[q], and ONE segw_pack_kernel launch
-// packs (before the exchange) or unpacks (after it) every block, the
-// contiguous ones as single-run maps.
-struct WSide {
-  mpigx_comm* c = nullptr;
-  int nseg = 0;
-  bool pack = false;
-  char* user = nullptr;  // the typed buffer
-  char* buf = nullptr;   // what vexchange addresses: user, or the temporary
-  char* tmp = nullptr;
-  long long total = 0;   // packed bytes, each block rounded up to 16
-  int type[kMaxRanks] = {};
-  long long cnt[kMaxRanks] = {}, dsp[kMaxRanks] = {}, off[kMaxRanks] = {}, len[kMaxRanks] = {};
-  ~WSide() {
-    if (tmp) tmp_put(c, tmp, 0);
-  }
-};
-
-// Checks only (nothing is allocated): every type slot must name a predefined
-// or committed type, even where its count is 0.
-static int wside_check(mpigx_comm* c, WSide* v, const void* user, int nseg, const int* counts, const int* displs,
-                       const int* types) {
-  v->c = c;
-  v->nseg = nseg;
-  v->user = (char*)user;
-  for (int q = 0; q < nseg; ++q)
-    if (counts[q] < 0) return MPIGX_ERR_COUNT;
-  for (int q = 0; q < nseg; ++q) {
-    rt::TypeDesc d;
-    if (rt::type_info(types[q], &d)) return MPIGX_ERR_TYPE;
-    v->type[q] = types[q];
-    v->cnt[q] = counts[q];
-    v->dsp[q] = displs[q];
-    v->len[q] = v->cnt[q] * d.size;
-    if (v->len[q] && !d.contig) v->pack = true;
-    v->total += (v->len[q] + 15) & ~15ll;
-  }
-  if (v->total && !user) return MPIGX_ERR_BUFFER;
-  return MPIGX_SUCCESS;
-}
-
-static int wside_place(WSide* v) {
-  long long at = 0;
-  for (int q = 0; q < v->nseg; ++q) {
-    v->off[q] = v->pack ? at : v->dsp[q];
-    at += (v->len[q] + 15) & ~15ll;
-  }
-  v->buf = v->user;
-  if (v->pack) {
-    if (!(v->tmp = tmp_get(v->c, v->total > 16 ? v->total : 16))) return MPIGX_ERR_NO_MEM;
-    v->buf = v->tmp;
-  }
-  return MPIGX_SUCCESS;
-}
-
-static int wside_move(WSide* v, int unpack) {
-  if (!v->pack) return MPIGX_SUCCESS;
-  rt::SegWSpec segs[kMaxRanks];
-  for (int q = 0; q < v->nseg; ++q) segs[q] = {v->type[q], v->cnt[q], v->dsp[q], v->off[q]};
-  const int rc = rt::type_pack_segw(v->user, v->nseg, segs, v->tmp, unpack, v->c->device, v->c->stream, nullptr);
-  if (!rc) v->c->unflagged = true;  // the final finish() drains the stream
-  return rc;
-}
-
-// MPI_Alltoallw: a datatype and a byte displacement per peer; MPI-2.2
-// IN_PLACE takes the send layout from the receive arguments.
 int mpigx_alltoallw(const void* sendbuf, const int* sendcounts, const int* sdispls, const int* sendtypes,
                     void* recvbuf, const int* recvcounts, const int* rdispls, const int* recvtypes, mpigx_comm_t c) {
-  int rc = check_comm(c);
-  if (rc) return rc;
-  const int n = c->n, r = c->rank;
-  const bool inplace = sendbuf == MPIGX_IN_PLACE;
-  if (!recvcounts || !rdispls || !recvtypes) return MPIGX_ERR_ARG;
-  if (!inplace && (!sendcounts || !sdispls || !sendtypes)) return MPIGX_ERR_ARG;
-  WSide S, R;
-  if ((rc = wside_check(c, &R, recvbuf, n, recvcounts, rdispls, recvtypes))) return rc;
-  if (!inplace && (rc = wside_check(c, &S, sendbuf, n, sendcounts, sdispls, sendtypes))) return rc;
-  if ((rc = wside_place(&R))) return rc;
-  if (!inplace && (rc = wside_place(&S))) return rc;
-  WSide& O = inplace ? R : S;
-  VSpec s;
-  s.ncopy = n;
-  for (int q = 0; q < n; ++q) {
-    s.c_slot[q] = q;
-    s.c_src[q] = O.off[q];
-    s.c_len[q] = O.len[q];
-    s.p_len[q] = R.len[q];
-    s.p_slot[q] = r;
-    s.p_dst[q] = R.off[q];
-  }
-  s.send = O.buf;
-  s.recv = R.buf;
-  rc = wside_move(&O, 0);
-  if (!rc) rc = vexchange(c, s);
-  if (!rc) rc = wside_move(&R, 1);
-  if (!rc) rc = finish(c);
-  return rc;
+  return alltoall_sides(sendbuf, sendcounts, sdispls, sendtypes, 0, recvbuf, recvcounts, rdispls, recvtypes, 0, true,
+                        c);
 }
 
 // ---------------------------------------------------------------------------
@@ -4158,7 +3967,7 @@ static int user_reduce(mpigx_comm* c, UserOp* u, const void* send, void* recv, i
   if (!all) return MPIGX_ERR_NO_MEM;
   int rc;
   if (kind == 1)
-    rc = gather_common(mine, (int)eb, MPIGX_BYTE, all, (int)eb, nullptr, nullptr, MPIGX_BYTE, root, c);
+    rc = gather_sides(mine, (int)eb, MPIGX_BYTE, all, (int)eb, nullptr, nullptr, MPIGX_BYTE, root, false, c);
   else
     rc = gather_like(mine, (int)eb, MPIGX_BYTE, all, (int)eb, MPIGX_BYTE, c, false);
   int hi = n - 1;  // fold x_lo .. x_hi

@@ -94,7 +94,7 @@ def test_full_shape_multi_vector(L):
 
 
 def test_local_u_variants(L):
-    """(~6 s) The 8-buffer shape at every vectors-per-thread variant
+    """(~1 s) The 8-buffer shape at every vectors-per-thread variant
     (common.hpp local_u, round 6): U = 1 / 2 / 4 forced through
     MPIGX_LOCAL_U on ragged sizes with Rabenseifner boundaries inside
     vectors, and the host's own choice on both sides of its threshold (f32:

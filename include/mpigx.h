@@ -345,11 +345,24 @@ int mpigx_reduce_scatter(const void *sendbuf, void *recvbuf, const int *recvcoun
 
 /* ---- local ops (config 2; operators.jl built-in Op set on device) ------- */
 /* MPI_Reduce_local (mpi.h:1357): inoutbuf[i] = op(inoutbuf[i], inbuf[i]).
- * Device pointers; blocking on the null stream. */
+ * Device pointers; blocking on the null stream.
+ * datatype: a predefined type, or a committed derived type whose bytes all
+ * belong to ONE predefined type (a strided SubArray's vector / subarray type,
+ * buffers.jl:104-117); count then counts instances, every buffer is read and
+ * written through the type map, the op applies per element of that
+ * predefined type (MPI_ERR_OP by MPICH's matrix for it) and bytes the type
+ * does not cover are never written.  A type over several predefined types is
+ * MPI_ERR_TYPE; more than 2^31-1 elements MPI_ERR_COUNT. */
 int mpigx_reduce_local(const void *inbuf, void *inoutbuf, int count, int datatype, int op);
 /* out[i] = fold_{k<nin} in[k][i] in `order` (as if in[k] were rank k's
  * buffer of an nin-rank Allreduce).  Device pointers; enqueued on `stream`
- * (NULL = null stream), asynchronous.  nin in [1, MPIGX_MAX_RANKS]. */
+ * (NULL = null stream), asynchronous.  nin in [1, MPIGX_MAX_RANKS].
+ * Derived datatypes as for mpigx_reduce_local, in and out all through the one
+ * type; out may be one of the inputs.  A contiguous derived type takes the
+ * predefined type's path.  A non-contiguous one folds in rank order: at
+ * nin <= 2 that is MPIGX_ORDER_MPICH's association too and both orders are
+ * accepted, at nin > 2 MPIGX_ORDER_MPICH is refused with MPIGX_ERR_ARG (the
+ * MPICH tree over many typed leaves is the packing collectives' business). */
 int mpigx_reduce_local_multi(const void *const *in, int nin, void *out, long long count,
                              int datatype, int op, int order, void *stream);
 
@@ -537,9 +550,11 @@ int mpigx_get_accumulate(const void *origin_addr, int origin_count, int origin_d
  * datatypes.jl:269-316), the byte-moving collectives (Bcast, Allgather,
  * Alltoall, Gather, Scatter and the v-collectives), which pack non-contiguous
  * types on device (pack_kernel, seg_pack_kernel) around the contiguous
- * algorithm, and one-sided Get / Put (typed_xfer_kernel).  Reductions and the
- * accumulate family accept derived types that are contiguous runs of one
- * predefined type.  lb / extent /
+ * algorithm, and one-sided Get / Put (typed_xfer_kernel).  The reducing
+ * collectives accept derived types that are contiguous runs of one predefined
+ * type; the local ops (mpigx_reduce_local, mpigx_reduce_local_multi) and the
+ * accumulate family also reduce through non-contiguous types whose bytes all
+ * belong to one predefined type (fold_typed_kernel, acc_typed_kernel).  lb / extent /
  * sizes follow MPICH 3.3.2 (tests/golden/types_golden.json). */
 #define MPIGX_ORDER_C 56
 #define MPIGX_ORDER_FORTRAN 57

@@ -371,6 +371,49 @@ struct AccTypedArgs {
   TypeRun runs[kAccTypedRuns];
   long long pfx[kAccTypedRuns + 1];
 };
+// Local fold through a non-contiguous type (kernels.hpp fold_typed_kernel):
+//   out[e] = ((in[0][e] op in[1][e]) op ...) op in[nin-1][e]
+// for every element e of the packed stream of the type's instances, the
+// rank-ordered fold of MPIGX_ORDER_LINEAR.  Bit k of in_typed: in[k] is read
+// through the type map (element e at in[k] + typed_off(e * esize)), else it
+// is packed (element e at in[k] + e * esize); out_typed likewise.  All typed
+// operands share the one map (runs / pfx: the type's device copies, staged in
+// LDS up to kFoldTypedRuns runs).  The stream is cut into `units` units of
+// `w` bytes: the widest power of two <= 16 that divides the type's geometry
+// and every pointer, but at least one element (an element aligned below its
+// size is moved in aligned pieces).
+// Two work splits, one rule (fold_typed_rows, below):
+//   element mode — thread t of the grid owns units t, t + nt, ... (nt threads),
+//     kFoldTypedU at a time, each resolved through the map per lane;
+//   row mode — wave v of the grid owns the packed bytes [v * S, (v + 1) * S),
+//     S = kFoldTypedU * kFoldTypedRow, then strides by the grid's waves; it
+//     walks them run block by run block in steps of at most kFoldTypedRow
+//     bytes, lane l taking the 16-B vector l of a step (w = 16).
+// Grid: one pass over everything up to kFoldTypedGridCap blocks, the kernel
+// strides over the rest.
+constexpr int kFoldTypedRuns = 64;  // = kInlineRuns (typed.hpp)
+constexpr int kFoldTypedU = 4;      // independent units per thread in flight
+constexpr int kFoldTypedIn = 4;     // inputs loaded per batch before any arithmetic
+constexpr int kFoldTypedGridCap = 1024;
+constexpr int kWave = 64;
+constexpr int kFoldTypedRow = kWave * 16;  // bytes one wave moves per step
+// Row mode when a wave fills a step inside every run: 16-B units and no run
+// shorter than a wave's worth of them.
+constexpr bool fold_typed_rows(long long min_run_len, int w) { return w == 16 && min_run_len >= kFoldTypedRow; }
+struct FoldTypedArgs {
+  const void* in[kMaxRanks];
+  void* out;
+  const TypeRun* runs;   // device copy, typemap order
+  const long long* pfx;  // packed bytes before run r within one instance (nruns + 1)
+  long long size, extent;
+  long long units;
+  int nin;
+  unsigned in_typed;
+  int out_typed;
+  int nruns;
+  int w;
+  int rows;  // 1: row mode
+};
 // Pack (typed -> contiguous) or unpack (contiguous -> typed) `units` W-byte
 // units of a packed stream of instances of one type (extent apart).
 struct PackArgs {

@@ -54,6 +54,7 @@
 #define MPIGX_SCAN_FN(K) MPIGX_CAT4(launch_scan_, MPIGX_OP_NAME(K), _o, K)
 #define MPIGX_ACC_FN(K) MPIGX_CAT4(launch_acc_, MPIGX_OP_NAME(K), _o, K)
 #define MPIGX_ACCT_FN(K) MPIGX_CAT4(launch_acc_typed_, MPIGX_OP_NAME(K), _o, K)
+#define MPIGX_FOLDT_FN(K) MPIGX_CAT4(launch_fold_typed_, MPIGX_OP_NAME(K), _o, K)
 
 namespace mpigx {
 namespace {
@@ -209,7 +210,8 @@ int occ_op(int kind, int a, int b) {
   hipError_t MPIGX_RING_FN(K)(dim3 grid, hipStream_t s, const RingArgs& a);                            \
   hipError_t MPIGX_SCAN_FN(K)(dim3 grid, hipStream_t s, const ScanArgs& a);                            \
   hipError_t MPIGX_ACC_FN(K)(dim3 grid, hipStream_t s, const AccArgs& a);                              \
-  hipError_t MPIGX_ACCT_FN(K)(dim3 grid, hipStream_t s, const AccTypedArgs& a);
+  hipError_t MPIGX_ACCT_FN(K)(dim3 grid, hipStream_t s, const AccTypedArgs& a);                        \
+  hipError_t MPIGX_FOLDT_FN(K)(dim3 grid, hipStream_t s, const FoldTypedArgs& a);
 MPIGX_DECL_OP(0) MPIGX_DECL_OP(1) MPIGX_DECL_OP(2) MPIGX_DECL_OP(3) MPIGX_DECL_OP(4) MPIGX_DECL_OP(5)
 MPIGX_DECL_OP(6) MPIGX_DECL_OP(7) MPIGX_DECL_OP(8) MPIGX_DECL_OP(9) MPIGX_DECL_OP(16) MPIGX_DECL_OP(17)
 #undef MPIGX_DECL_OP
@@ -252,6 +254,14 @@ MPIGX_DECL_OP(6) MPIGX_DECL_OP(7) MPIGX_DECL_OP(8) MPIGX_DECL_OP(9) MPIGX_DECL_O
   hipError_t MPIGX_ACCT_FN(K)(dim3 grid, hipStream_t s, const AccTypedArgs& a) {                       \
     if constexpr (valid_op(K)) {                                                                       \
       hipLaunchKernelGGL((acc_typed_kernel<OpOf<K>::type, T>), grid, dim3(kThreads), 0, s, a);         \
+      return hipGetLastError();                                                                        \
+    }                                                                                                  \
+    return hipErrorInvalidValue;                                                                       \
+  }                                                                                                    \
+  hipError_t MPIGX_FOLDT_FN(K)(dim3 grid, hipStream_t s, const FoldTypedArgs& a) {                     \
+    if constexpr (valid_op(K)) {                                                                       \
+      if (a.rows) hipLaunchKernelGGL((fold_typed_kernel<OpOf<K>::type, T, 1>), grid, dim3(kThreads), 0, s, a); \
+      else hipLaunchKernelGGL((fold_typed_kernel<OpOf<K>::type, T, 0>), grid, dim3(kThreads), 0, s, a); \
       return hipGetLastError();                                                                        \
     }                                                                                                  \
     return hipErrorInvalidValue;                                                                       \
@@ -357,6 +367,10 @@ hipError_t MPIGX_CAT(launch_acc_typed_, MPIGX_REP_NAME)(int op, dim3 grid, hipSt
   if (op == O_REPLACE) return MPIGX_ACCT_FN(16)(grid, s, a);
   if (op == O_NOOP) return MPIGX_ACCT_FN(17)(grid, s, a);
   MPIGX_SWITCH(MPIGX_ACCT_FN, grid, s, a)
+}
+// the local LINEAR fold through a derived type (fold_typed_kernel), collective op set
+hipError_t MPIGX_CAT(launch_fold_typed_, MPIGX_REP_NAME)(int op, dim3 grid, hipStream_t s, const FoldTypedArgs& a) {
+  MPIGX_SWITCH(MPIGX_FOLDT_FN, grid, s, a)
 }
 #undef MPIGX_SWITCH
 #else

@@ -31,4 +31,7 @@ hipError_t MPIGX_CAT(launch_acc_, MPIGX_REP_NAME)(int, dim3, hipStream_t, const 
 hipError_t MPIGX_CAT(launch_acc_typed_, MPIGX_REP_NAME)(int, dim3, hipStream_t, const AccTypedArgs&) {
   return hipErrorInvalidValue;
 }
+hipError_t MPIGX_CAT(launch_fold_typed_, MPIGX_REP_NAME)(int, dim3, hipStream_t, const FoldTypedArgs&) {
+  return hipErrorInvalidValue;
+}
 }  // namespace mpigx

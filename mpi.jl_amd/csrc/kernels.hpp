@@ -1216,4 +1216,224 @@ __global__ __launch_bounds__(kThreads) void acc_typed_kernel(AccTypedArgs A) {
   pull_release(A.coherent);
 }
 
+// ---------------------------------------------------------------------------
+// fold_typed_kernel<OP,T,ROWS>: the local LINEAR fold through a derived
+// datatype (common.hpp FoldTypedArgs) — a gather / fold / scatter in which the
+// nin inputs and the output share ONE address map, so a unit's typed offset is
+// resolved once and reused for every operand (a packed operand takes the
+// unit's packed offset instead: one select per operand, no second map).
+//
+// A thread holds kFoldTypedU units.  All their offsets are resolved first;
+// then, per batch of kFoldTypedIn inputs (a runtime loop: nin does not
+// multiply the instantiations), the loads of every unit of the batch are
+// issued before any arithmetic; then the fold, in rank order with the running
+// value as inout (fold_leaves' S_LINEAR: same ops, roles and bf16 rounding),
+// then the stores.  The thread that stores a unit is the one that loaded it
+// from every input, after those loads: out may alias a typed input.
+//
+// Data stays in registers as raw aligned pieces (FoldUnit; AccRaw's reason);
+// the arithmetic sees them as Vec<T, W>, so a unit of several elements folds
+// with the vector ops of the contiguous kernels.  The run table and the input
+// pointers are read with run-time indices: both are staged in LDS (kernel
+// arguments indexed that way went to scratch, see acc_typed_kernel); a table
+// of more than kFoldTypedRuns runs is read from the type's device copy.
+// ---------------------------------------------------------------------------
+template <class T, int W>
+struct FoldUnit {
+  static constexpr int UB = W * (int)sizeof(T);
+  // a lone complex element may be aligned to its component only
+  static constexpr int P = (W == 1 && is_cplx<T>::v) ? UB / 2 : UB;
+  static constexpr int NP = UB / P;
+  using R = typename AccRaw<P>::type;
+  R r[NP];
+};
+template <class T, int W>
+__device__ __forceinline__ void fu_ld(FoldUnit<T, W>& d, const char* p) {
+  using R = typename FoldUnit<T, W>::R;
+#pragma unroll
+  for (int i = 0; i < FoldUnit<T, W>::NP; ++i) d.r[i] = MPIGX_GPTR(const R, p)[i];
+}
+template <class T, int W>
+__device__ __forceinline__ void fu_st(char* p, const FoldUnit<T, W>& d) {
+  using R = typename FoldUnit<T, W>::R;
+#pragma unroll
+  for (int i = 0; i < FoldUnit<T, W>::NP; ++i) MPIGX_GPTR(R, p)[i] = d.r[i];
+}
+template <class OP, class T, int W>
+__device__ __forceinline__ void fu_apply(FoldUnit<T, W>& a, const FoldUnit<T, W>& b) {  // a = inout
+  Vec<T, W> x, y;
+  static_assert(sizeof(x.x) == sizeof(a.r), "a unit is one register vector");
+  __builtin_memcpy(x.x, a.r, sizeof(a.r));
+  __builtin_memcpy(y.x, b.r, sizeof(b.r));
+  vapply<OP, T, W>(x, x, y);
+  __builtin_memcpy(a.r, x.x, sizeof(a.r));
+}
+
+// U units of W elements: typed offsets to[], packed offsets po[], on[] = this
+// lane has the unit (the last pass of a range, a partial row step).
+template <class OP, class T, int W, int U>
+__device__ __forceinline__ void fold_typed_units(const FoldTypedArgs& A, const char* const* sin,
+                                                 const long long (&to)[U], const long long (&po)[U],
+                                                 const bool (&on)[U]) {
+  constexpr int NB = kFoldTypedIn;
+  FoldUnit<T, W> acc[U];
+  const int nin = A.nin;
+  const unsigned ty = A.in_typed;
+  for (int k0 = 0; k0 < nin; k0 += NB) {
+    FoldUnit<T, W> v[NB][U];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+      if (k0 + j < nin) {
+        const char* p = sin[k0 + j];
+        const bool t = (ty >> (k0 + j)) & 1u;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (on[u]) fu_ld(v[j][u], p + (t ? to[u] : po[u]));
+      }
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+      if (k0 + j < nin) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (j == 0 && k0 == 0) acc[u] = v[0][u];
+          else fu_apply<OP, T, W>(acc[u], v[j][u]);
+        }
+      }
+  }
+  char* out = (char*)A.out;
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (on[u]) fu_st(out + (A.out_typed ? to[u] : po[u]), acc[u]);
+}
+
+// a wave-uniform value, held in scalar registers from here on
+__device__ __forceinline__ long long wave_uniform(long long v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ TypeRun wave_uniform(const TypeRun& r) {
+  return TypeRun{wave_uniform(r.off), wave_uniform(r.len), wave_uniform(r.n), wave_uniform(r.stride)};
+}
+
+// Element mode: the map per lane, kFoldTypedU units apart by the grid's thread
+// count so that a wave's packed accesses coalesce.  The offsets do not depend
+// on how a unit is folded, so they are resolved once, ahead of the choice of
+// the unit's vector type: w = unit bytes (A.w, or one element when the
+// alignment is below it); WIDE = false folds one element per unit only.
+template <class OP, class T, bool WIDE>
+__device__ __forceinline__ void fold_typed_elem(const FoldTypedArgs& A, const char* const* sin, const TypeRun* runs,
+                                                const long long* pfx) {
+  constexpr int U = kFoldTypedU;
+  constexpr int ES = (int)sizeof(T);
+  const int w = (WIDE && A.w > ES) ? A.w : ES;
+  const long long n = A.units, nt = (long long)gridDim.x * blockDim.x;
+  const long long size = A.size, extent = A.extent;
+  const int nruns = A.nruns;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += U * nt) {
+    long long to[U], po[U];
+    bool on[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      on[u] = i + u * nt < n;
+      po[u] = (i + u * nt) * w;
+      // (a lane past the end resolves an offset it never uses; the map reads
+      // only the run table)
+      to[u] = typed_off(runs, pfx, nruns, size, extent, po[u]);
+    }
+    if constexpr (WIDE && ES < 16) {
+      if (w == 16) { fold_typed_units<OP, T, 16 / ES, U>(A, sin, to, po, on); continue; }
+    }
+    if constexpr (WIDE && ES < 8) {
+      if (w == 8) { fold_typed_units<OP, T, 8 / ES, U>(A, sin, to, po, on); continue; }
+    }
+    if constexpr (WIDE && ES < 4) {
+      if (w == 4) { fold_typed_units<OP, T, 4 / ES, U>(A, sin, to, po, on); continue; }
+    }
+    if constexpr (WIDE && ES < 2) {
+      if (w == 2) { fold_typed_units<OP, T, 2, U>(A, sin, to, po, on); continue; }
+    }
+    fold_typed_units<OP, T, 1, U>(A, sin, to, po, on);
+  }
+}
+
+// Row mode (16-B units, every run at least kFoldTypedRow bytes): a wave takes
+// the packed bytes [s0, s0 + U * kFoldTypedRow), resolves s0 once — instance,
+// run, block, byte, all wave-uniform — and walks on from there by addition:
+// a step is at most kFoldTypedRow bytes and never crosses a block's end, lane l
+// takes its vector l.  No per-lane divide or search; inside a run every access
+// is a full coalesced 16-B vector.
+template <class OP, class T>
+__device__ __forceinline__ void fold_typed_rows_body(const FoldTypedArgs& A, const char* const* sin,
+                                                     const TypeRun* runs, const long long* pfx) {
+  constexpr int U = kFoldTypedU;
+  constexpr int W = VecW<T>::v;
+  constexpr long long S = (long long)U * kFoldTypedRow;
+  const long long lane16 = (long long)(threadIdx.x % kWave) * 16;
+  const long long nw = (long long)gridDim.x * (kThreads / kWave);
+  const long long w0 = wave_uniform((long long)blockIdx.x * (kThreads / kWave) + threadIdx.x / kWave);
+  const long long total = A.units * 16, size = A.size, extent = A.extent;
+  const int nruns = A.nruns;
+  for (long long s0 = w0 * S; s0 < total; s0 += nw * S) {
+    const long long end = lmin(s0 + S, total);
+    const TypedPos t = typed_pos(runs, pfx, nruns, size, s0);
+    long long k = wave_uniform(t.k), i = wave_uniform(t.i), b = wave_uniform(t.b), p = s0;
+    int r = __builtin_amdgcn_readfirstlane(t.run);
+    TypeRun R = wave_uniform(runs[r]);
+    while (p < end) {
+      long long to[U], po[U];
+      bool on[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long long take = lmin(lmin(R.len - b, (long long)kFoldTypedRow), end - p);
+        to[u] = k * extent + R.off + i * R.stride + b + lane16;
+        po[u] = p + lane16;
+        on[u] = lane16 < take;
+        p += take;
+        b += take;
+        if (b == R.len) {  // next block, run, instance
+          b = 0;
+          if (++i == R.n) {
+            i = 0;
+            if (++r == nruns) {
+              r = 0;
+              ++k;
+            }
+            R = wave_uniform(runs[r]);
+          }
+        }
+      }
+      fold_typed_units<OP, T, W, U>(A, sin, to, po, on);
+    }
+  }
+}
+
+template <class OP, class T, int ROWS>
+__global__ __launch_bounds__(kThreads) void fold_typed_kernel(FoldTypedArgs A) {
+  __shared__ TypeRun sruns[kFoldTypedRuns];
+  __shared__ long long spfx[kFoldTypedRuns + 1];
+  __shared__ const char* sin[kMaxRanks];
+  const bool inl = A.nruns <= kFoldTypedRuns;
+  if (inl) {
+    for (int i = threadIdx.x; i < A.nruns; i += blockDim.x) sruns[i] = A.runs[i];
+    for (int i = threadIdx.x; i <= A.nruns; i += blockDim.x) spfx[i] = A.pfx[i];
+  }
+  {
+    const char* const* in = reinterpret_cast<const char* const*>(&A.in[0]);
+    for (int i = threadIdx.x; i < kMaxRanks; i += blockDim.x) sin[i] = in[i];
+  }
+  __syncthreads();
+  if constexpr (ROWS) {
+    // (the host takes row mode only with the table in LDS)
+    fold_typed_rows_body<OP, T>(A, sin, sruns, spfx);
+  } else {
+    // (two calls, not a select of the table pointers: the LDS table is read
+    // with LDS instructions, the long one with global loads.  Long tables —
+    // subarrays flattened to many runs — fold one element per unit, which
+    // keeps this rare path to one body; the host sets w accordingly)
+    if (inl) fold_typed_elem<OP, T, true>(A, sin, sruns, spfx);
+    else fold_typed_elem<OP, T, false>(A, sin, A.runs, A.pfx);
+  }
+}
+
 }  // namespace mpigx

@@ -4014,7 +4014,8 @@ static int user_reduce(mpigx_comm* c, UserOp* u, const void* send, void* recv, i
 }
 
 // Reductions over a derived type: only contiguous runs of ONE predefined type
-// (MPI allows predefined ops on such types; they reduce element-wise).
+// (MPI allows predefined ops on such types; they reduce element-wise).  The
+// local ops also take non-contiguous ones (mpigx_reduce_local_multi).
 static int lower_reduce_type(int* datatype, int* count) {
   if (!derived(*datatype)) return MPIGX_SUCCESS;
   rt::TypeDesc d;
@@ -4515,15 +4516,35 @@ int mpigx_reduce_local_multi(const void* const* in, int nin, void* out, long lon
                              int order, void* stream) {
   const TypeInfo* t;
   int oc;
-  int rc = validate(datatype, op, &t, &oc);
+  // a derived type reduces element-wise over the predefined type all its
+  // bytes belong to; count counts instances
+  rt::TypeDesc d;
+  const int typed = derived(datatype);
+  if (typed && (rt::type_info(datatype, &d) || d.basic == 0)) return MPIGX_ERR_TYPE;
+  int rc = validate(typed ? d.basic : datatype, op, &t, &oc);
   if (rc) return rc;
   if (nin < 1 || nin > kMaxRanks) return MPIGX_ERR_ARG;
   if (order != MPIGX_ORDER_MPICH && order != MPIGX_ORDER_LINEAR) return MPIGX_ERR_ARG;
   if (count < 0) return MPIGX_ERR_COUNT;
+  const long long instances = count;
+  if (typed) {
+    if (count > 0x7fffffffll || count * d.size / t->size > 0x7fffffffll) return MPIGX_ERR_COUNT;
+    count = count * d.size / t->size;  // elements, from here on
+  }
+  // at nin <= 2 both orders are the one association (in[0] op in[1], in[0]
+  // as inout); the MPICH tree over more leaves of a non-contiguous type is
+  // left to the collective paths, which pack
+  if (typed && !d.contig && nin > 2 && order != MPIGX_ORDER_LINEAR) return MPIGX_ERR_ARG;
   if (count == 0) return MPIGX_SUCCESS;
   if (!in || !out) return MPIGX_ERR_BUFFER;
   for (int k = 0; k < nin; ++k)
     if (!in[k]) return MPIGX_ERR_BUFFER;
+  if (typed && !d.contig) {
+    int dev = 0;
+    HIPCK(hipGetDevice(&dev));
+    return rt::type_fold(datatype, in, nin, (1u << nin) - 1u, out, 1, instances, t->rep, t->size, oc,
+                         env_ll("MPIGX_LOCAL_MAX_BLOCKS", 0), dev, (hipStream_t)stream);
+  }
   FoldArgs a;
   memset(&a, 0, sizeof a);
   a.mode = M_LOCAL;

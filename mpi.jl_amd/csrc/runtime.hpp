@@ -443,6 +443,14 @@ int type_elem_aligned(int datatype, long long es);
 // typed_xfer_kernel); flat_xfer: contiguous src, destination type as runs.
 int type_xfer(int stype, const void* src, int dtype, void* dst, long long bytes, int device, hipStream_t s);
 int flat_xfer(const RmaType& d, void* dst, const void* src, long long bytes, hipStream_t s);
+// out = LINEAR fold of in[0..nin) over `count` instances of a committed
+// NON-contiguous type whose bytes all belong to the predefined type (rep,
+// esize) — kernels.hpp fold_typed_kernel, enqueued on `s`.  Bit k of in_typed /
+// out_typed: that operand is read / written through the type map, else it is
+// the packed stream (so a caller can fuse pack + fold or fold + unpack).
+// max_blocks > 0 caps the grid below the launch's own cap.
+int type_fold(int datatype, const void* const* in, int nin, unsigned in_typed, void* out, int out_typed,
+              long long count, int rep, int esize, int oc, long long max_blocks, int device, hipStream_t s);
 // pooled device temporaries of the communicator (mpigx.cpp tmp_get / tmp_put)
 char* tmp_alloc(mpigx_comm* c, long long bytes);
 void tmp_release(mpigx_comm* c, char* p);

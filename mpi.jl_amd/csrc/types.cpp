@@ -473,6 +473,61 @@ int flat_xfer(const RmaType& d, void* dst, const void* src, long long bytes, hip
   return MPIGX_SUCCESS;
 }
 
+namespace {
+FoldTypedLauncher fold_typed_launcher(int rep) {
+  static const FoldTypedLauncher ls[R_COUNT] = {
+      launch_fold_typed_i8,  launch_fold_typed_u8,  launch_fold_typed_i16, launch_fold_typed_u16, launch_fold_typed_i32,
+      launch_fold_typed_u32, launch_fold_typed_i64, launch_fold_typed_u64, launch_fold_typed_f32, launch_fold_typed_f64,
+      launch_fold_typed_c64, launch_fold_typed_c128, launch_fold_typed_bf16};
+  return rep >= 0 && rep < R_COUNT ? ls[rep] : nullptr;
+}
+}  // namespace
+
+int type_fold(int h, const void* const* in, int nin, unsigned in_typed, void* out, int out_typed, long long count,
+              int rep, int esize, int oc, long long max_blocks, int device, hipStream_t s) {
+  DType* t = lookup(h);
+  if (!t || !t->committed || t->runs.empty() || nin < 1 || nin > kMaxRanks) return MPIGX_ERR_TYPE;
+  const long long bytes = count * t->size;
+  if (bytes <= 0) return MPIGX_SUCCESS;
+  FoldTypedLauncher L = fold_typed_launcher(rep);
+  if (!L) return MPIGX_ERR_TYPE;
+  FoldTypedArgs a;
+  memset(&a, 0, sizeof a);
+  int rc = device_runs(t, device, &a.runs, &a.pfx);
+  if (rc) return rc;
+  // the unit divides the type's geometry (pack's rule) and every operand pointer
+  unsigned long long ptrs = (unsigned long long)(uintptr_t)out;
+  long long min_len = t->runs[0].len;
+  for (int k = 0; k < nin; ++k) {
+    a.in[k] = in[k];
+    ptrs |= (unsigned long long)(uintptr_t)in[k];
+  }
+  for (const auto& r : t->runs) min_len = std::min(min_len, r.len);
+  a.w = unit_of(*t, (const void*)(uintptr_t)ptrs, nullptr, bytes);
+  a.nruns = (int)t->runs.size();
+  // a table too long for LDS is searched in global memory: one element per unit
+  if (a.nruns > kFoldTypedRuns && a.w > esize) a.w = esize;
+  a.rows = a.nruns <= kFoldTypedRuns && fold_typed_rows(min_len, a.w);
+  a.out = out;
+  a.nin = nin;
+  a.in_typed = in_typed;
+  a.out_typed = out_typed;
+  a.size = t->size;
+  a.extent = t->ub - t->lb;
+  a.units = bytes / std::max(a.w, esize);
+  // one pass over everything up to the cap, the kernel strides over the rest
+  // (either mode: a thread's kFoldTypedU units, a wave's kFoldTypedU steps of kWave vectors)
+  const long long per_block = (long long)kFoldTypedU * kThreads;
+  long long g = (a.units + per_block - 1) / per_block;
+  g = std::min(g, (long long)kFoldTypedGridCap);
+  if (max_blocks > 0) g = std::min(g, max_blocks);
+  if (L(oc, dim3((unsigned)std::max(1ll, g)), s, a) != hipSuccess) {
+    (void)hipGetLastError();
+    return MPIGX_ERR_INTERN;
+  }
+  return MPIGX_SUCCESS;
+}
+
 }  // namespace rt
 }  // namespace mpigx
 

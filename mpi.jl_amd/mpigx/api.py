@@ -1277,17 +1277,22 @@ def Exscan(sendbuf, op, comm):
 # ---------------------------------------------------------------------------
 # local op (config 2): the built-in MPI.Op set on device buffers
 # ---------------------------------------------------------------------------
-def Reduce_local_(inbuf, inoutbuf, count, op):
-    """MPI_Reduce_local (mpi.h:1357): inoutbuf = op(inoutbuf, inbuf)."""
-    T = _eltype(inoutbuf)
+def Reduce_local_(inbuf, inoutbuf, count, op, datatype=None):
+    """MPI_Reduce_local (mpi.h:1357): inoutbuf = op(inoutbuf, inbuf).  datatype: a
+    committed derived Datatype over the buffers' element type (count instances,
+    both buffers through its type map); default: the element type."""
+    T = _eltype(inoutbuf) if datatype is None else datatype
     opx = _as_op(op, _dtype(inoutbuf))
     _check(lib().mpigx_reduce_local(_ptr(inbuf), _ptr(inoutbuf), _cint(count), T.val, opx.val))
     return inoutbuf
 
 
-def reduce_local_multi(inputs, out, op, order=C.MPIGX_ORDER_MPICH, stream=None, count=None):
+def reduce_local_multi(inputs, out, op, order=C.MPIGX_ORDER_MPICH, stream=None, count=None, datatype=None):
     """out = fold(inputs) as an len(inputs)-rank Allreduce would (asynchronous,
-    on `stream` (torch stream or raw handle; default: current stream))."""
+    on `stream` (torch stream or raw handle; default: current stream)).
+    datatype: a committed derived Datatype over out's element type, applied to
+    every input and to out (count, required then, counts instances; a
+    non-contiguous type needs MPIGX_ORDER_LINEAR beyond two inputs)."""
     torch = _torch()
     n = len(inputs)
     arr = (ctypes.c_void_p * n)(*[t.data_ptr() for t in inputs])
@@ -1295,8 +1300,10 @@ def reduce_local_multi(inputs, out, op, order=C.MPIGX_ORDER_MPICH, stream=None, 
         stream = torch.cuda.current_stream(out.device).cuda_stream
     elif hasattr(stream, "cuda_stream"):
         stream = stream.cuda_stream
-    T = _eltype(out)
+    T = _eltype(out) if datatype is None else datatype
     opx = _as_op(op, out.dtype)
+    if datatype is not None and count is None:
+        raise ValueError("reduce_local_multi: a datatype needs an explicit count of instances")
     cnt = out.numel() if count is None else count
     _check(lib().mpigx_reduce_local_multi(arr, n, ctypes.c_void_p(out.data_ptr()), cnt, T.val, opx.val, order,
                                           ctypes.c_void_p(stream)))
